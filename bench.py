@@ -14,6 +14,11 @@ tiles (images are independent fits): weak scaling, no data-path 
 carries only the max-over-ranks time and the per-image metric records.  Inputs are resident in HBM
 when the timed region starts; host work that belongs to the path (the permutations of
 torch.randperm order) is inside the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps once and prints the headline; --dump-outputs DIR also writes what the
+last timed step computed.  --full adds what the headline does not need: three repeats (the median is reported), the
+per-image records, one tile alone, the roofline probe and the accounting, the short legs of the other configurations
+and the CPU baseline.
 """
 import argparse
 import json
@@ -57,11 +62,19 @@ def parse():
                    help="BASELINE.json configs[4]: USE_COORDINATES=True + EMBEDDING=True (F = 250)")
     p.add_argument("--in-flight", type=int, default=4,
                    help="tiles progressing at a time on each GPU (independent fits on their own streams)")
-    p.add_argument("--repeats", type=int, default=3, help="repeats of the timed region; the median is reported")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--repeats", type=int, default=None,
+                   help="repeats of the timed region; the median is reported (default: 1, and 3 with --full)")
+    p.add_argument("--full", action="store_true",
+                   help="measure and check beyond the headline: three repeats, the per-image records, one tile alone, the "
+                        "roofline probe and the tile's accounting, the legs of the other configurations and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float32): the best and the 16-bit "
+                        "weights, the evaluation log and the decoded raster (a fixed, seeded sample of 2^23 sub-pixels "
+                        "where it has more)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--no-other-configs", action="store_true",
-                   help="skip the short legs of BASELINE.json configs[2] (bc = 256) and configs[4] (coordinates + embedding) "
-                        "that a default one-GPU run of the headline configuration appends as `other_configs`")
+                   help="with --full: skip the short legs of BASELINE.json configs[2] (bc = 256) and configs[4] (coordinates + "
+                        "embedding) that a one-GPU run of the headline configuration appends as `other_configs`")
     p.add_argument("--cpu-sample", type=int, default=512, help="side of the CPU-baseline crop")
     p.add_argument("--cpu-full-epochs", type=int, default=10,
                    help="epochs of form B (vectorised) measured on the WHOLE tile, scaled to the full recipe (0: skip)")
@@ -70,6 +83,8 @@ def parse():
     a = p.parse_args()
     if a.steps is None:
         a.steps = 16 if a.gpus == 1 else 8
+    if a.repeats is None:
+        a.repeats = 3 if a.full else 1
     return a
 
 
@@ -569,6 +584,26 @@ def accounting(a, roof, fits_per_launch, ms_per_tile, decode_ms):
                     "bound the tile together: profiles/r06_bounds_in_flight.txt, DESIGN.md 4.0"}
 
 
+DUMP_SAMPLE = 1 << 23     # sub-pixels of the decoded raster written at most: 32 MiB of float32
+
+
+def dump_outputs(d, codec, fit, rec):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 .npy files -- the fit's best
+    weights, the 16-bit weights the bitstream carries and the decode ran on, the evaluation log [epochs, (mse, improved)]
+    and the decoded raster (uint16 values, exact in float32), flattened [C*H*W]; above DUMP_SAMPLE sub-pixels, only those
+    at DUMP_SAMPLE positions drawn without replacement by a generator seeded with SEED, in increasing order: the same
+    positions in every run of one shape."""
+    os.makedirs(d, exist_ok=True)
+    flat = rec.reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(SEED).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+        flat = flat[torch.from_numpy(pos).to(flat.device)]
+    out = {"best_params": fit.best_params, "params_16bit": codec.truncate_device(fit.best_params, 16),
+           "eval_mse_log": fit.mse_log, "raster": (flat.to(torch.int32) & 0xFFFF).float()}
+    for name, v in out.items():
+        np.save(os.path.join(d, name + ".npy"), v.float().cpu().numpy())
+
+
 def launch_ranks(a):
     """`python bench.py --gpus N` with N > 1 and no launcher: start N ranks, one per GPU, BEFORE this process makes
     any GPU call (it never does), relay rank 0's JSON line, fail if any rank fails.  Same environment contract as
@@ -693,7 +728,10 @@ def main():
     # resident in HBM before the clock starts
     total = a.warmup + a.steps
     mine = shard.assign(total * world, rank, world)
-    tiles = [ops.to_device_u16(synthetic_tile(i, a.bands, a.height, a.width), dev) for i in mine]
+    # (numpy releases the GIL in the bulk of synthetic_tile: ~1.7 s a full-size tile alone, threads cut the set-up several-fold)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=max(1, min(16, os.cpu_count() or 1, len(mine)))) as pool:
+        tiles = [ops.to_device_u16(img, dev) for img in pool.map(lambda i: synthetic_tile(i, a.bands, a.height, a.width), mine)]
     torch.cuda.synchronize()
 
     def barrier():
@@ -707,7 +745,7 @@ def main():
     for _ in range(2 if a.warmup else 0):
         run_images(codec, ops, tiles[:a.warmup] * max(1, min(a.in_flight, a.steps)), a, path)
     # the timed region -- exactly K tiles per GPU between two barrier + synchronize pairs, maximum over the ranks -- runs
-    # `--repeats` times (default 3); the line carries the MEDIAN repeat and the spread
+    # `--repeats` times (default 1, 3 with --full); the line carries the MEDIAN repeat and the spread
     rep_laps, own = [], []
     for _ in range(a.repeats):
         barrier()
@@ -720,20 +758,23 @@ def main():
     mid = order[len(order) // 2]
     elapsed = rep_laps[mid]
     rank_elapsed = shard.gather_records([[float(rank), own[mid] * 1e3]], 2, xdev)   # every rank's own clock, that repeat
-
-    # per-image metric records (after the clock): [image index, reconstruction MSE, best evaluation MSE] for every
-    # timed tile -- the only data the ranks exchange
-    recs = []
-    for idx, img_d, (fit, rec) in zip(mine[a.warmup:], tiles[a.warmup:], done):
-        diff = (img_d.view(torch.int16).to(torch.int32) & 0xFFFF).float() - (rec.to(torch.int32) & 0xFFFF).float()
-        recs.append([float(idx), float((diff * diff).mean().item()), float(fit.mse_log[:, 0].min().item())])
-    records = shard.gather_records(recs, 3, xdev)
     fit, rec = done[-1]
-    img_d, mse = tiles[-1], recs[-1][1]
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, codec, fit, rec)
+
+    if a.full:
+        # per-image metric records (after the clock): [image index, reconstruction MSE, best evaluation MSE] for every
+        # timed tile -- the only data the ranks exchange
+        recs = []
+        for idx, img_d, (fit, rec) in zip(mine[a.warmup:], tiles[a.warmup:], done):
+            diff = (img_d.view(torch.int16).to(torch.int32) & 0xFFFF).float() - (rec.to(torch.int32) & 0xFFFF).float()
+            recs.append([float(idx), float((diff * diff).mean().item()), float(fit.mse_log[:, 0].min().item())])
+        records = shard.gather_records(recs, 3, xdev)
+        img_d, mse = tiles[-1], recs[-1][1]
 
     # one tile alone on the GPU (BASELINE.json configs[1] is "a single tile"): rank 0, after the clock
     single = None
-    if rank == 0:
+    if rank == 0 and a.full:
         single = lone_tile(codec, ops, tiles[-1], a, path)
         # the launch sequence the timed region runs (pairs of fits per launch, four host threads) against the same fit
         # alone: bit-identical weights and raster, or the line says so
@@ -761,6 +802,9 @@ def main():
                        "tiles_per_launch": tiles_per_launch(a, ops, path),
                        "warmup_note": "the warm-up tiles run twice on each in-flight stream",
                        "parallelism": f"image-sharded x{world}", "path": a.path},
+        }
+    if rank == 0 and a.full:
+        out.update({
             "single_tile_ms": round(single["ms"], 3),
             "single_tile_encode_ms": round(single["encode_ms"], 3), "single_tile_decode_ms": round(single["decode_ms"], 3),
             "single_tile_mpixels_per_s": round(px / single["ms"] / 1e3, 4),
@@ -773,7 +817,7 @@ def main():
             "recon_mse_last_tile": round(mse, 4),
             "recon_psnr_last_tile": round(10 * np.log10(10000 ** 2 / max(mse, 1e-12)), 3),
             "records": records,
-        }
+        })
         out["roofline"] = roofline_probe(codec, ops, fit, img_d, a, path)
         # whole job against the matrix peak: algorithmic FLOPs of every timed tile (10 train + 10 evaluation passes + decode)
         tile_flop = tile_flops(a, ops, fit, path)
@@ -806,6 +850,7 @@ def main():
             }
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a)
+    if rank == 0:
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

@@ -2,7 +2,7 @@
 # Builds lbdrn-msic_amd/liblbdrn_hip_two.so = the library with scripts/experiments/two_workgroups_per_cu.patch applied
 # (the TWO mode of k_train_stream: two training workgroups per CU), in a scratch copy of csrc/ -- the tree
 # itself is not touched.  Run the variant with
-#     LBDRN_HIP_LIB=$PWD/lbdrn-msic_amd/liblbdrn_hip_two.so LBDRN_STREAM2=1 python3 bench.py --no-cpu-baseline --no-other-configs
+#     LBDRN_HIP_LIB=$PWD/lbdrn-msic_amd/liblbdrn_hip_two.so LBDRN_STREAM2=1 python3 bench.py --full --no-cpu-baseline --no-other-configs
 # (LBDRN_STREAM2 unset: the same library runs the shipped one-workgroup-per-CU kernel -- the A/B of DESIGN.md 4.1).
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)

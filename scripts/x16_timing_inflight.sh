@@ -2,7 +2,7 @@
 # shipped one, by fits in flight: is the tile bound by the training launch or by the rest of a chain's step?
 for infl in 4 6 8; do for v in base x16t; do
   if [ "$v" = base ]; then unset LBDRN_HIP_LIB; else export LBDRN_HIP_LIB=lbdrn-msic_amd/liblbdrn_hip_$v.so; fi
-  python bench.py --in-flight $infl --steps $((infl*3)) --warmup $infl --repeats 2 --no-cpu-baseline --no-other-configs > /tmp/g.json 2>/dev/null
+  python bench.py --full --in-flight $infl --steps $((infl*3)) --warmup $infl --repeats 2 --no-cpu-baseline --no-other-configs > /tmp/g.json 2>/dev/null
   python - "$infl" "$v" <<'PY'
 import json,sys
 d=json.loads(open("/tmp/g.json").read().strip().splitlines()[-1])

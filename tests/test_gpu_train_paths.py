@@ -679,14 +679,14 @@ def test_fits_of_a_group_step_side_by_side_and_equal_fits_one_by_one(dev):
 
 
 def test_bench_prints_one_json_line_with_the_contract_keys(dev):
-    """bench.py on a small tile (same code path as the full-size run): exactly one JSON line on stdout with the
+    """bench.py --full on a small tile (same code path as the full-size run): exactly one JSON line on stdout with the
     driver's keys, the roofline and cpu_baseline objects, and values of the right kind."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                          "--height", "192", "--width", "256", "-bs", "2048", "-e", "3", "--cpu-sample", "48"],
+                          "--height", "192", "--width", "256", "-bs", "2048", "-e", "3", "--cpu-sample", "48", "--full"],
                          check=True, env=env, capture_output=True, text=True, timeout=900).stdout
     lines = [ln for ln in out.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -723,6 +723,42 @@ def test_bench_prints_one_json_line_with_the_contract_keys(dev):
     assert r["apply_pass_x16_ms_opt_in"] > 0 and "LBDRN_EVAL_X16" not in r["apply_pass"]
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(dev, tmp_path):
+    """bench.py without --full: one JSON line with the headline keys and nothing the headline does not need, the timed
+    region run once over exactly --steps tiles; --dump-outputs holds the last timed tile's fit and raster, bit for bit what
+    the same tile fitted alone in this process gives."""
+    import json
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    d_out = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--height", "192", "--width", "256", "-bs", "2048", "-e", "3", "--dump-outputs", str(d_out)],
+                         check=True, env=env, capture_output=True, text=True, timeout=900).stdout
+    lines = [ln for ln in out.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert key in d, key
+    for key in ("roofline", "cpu_baseline", "single_tile_ms", "records", "accounting", "other_configs"):
+        assert key not in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["repeats"] == 1 and len(d["ms_per_step_all_repeats"]) == 1
+    assert d["unit"] == "Mpixels/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 192 * 256 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-3 * d["value"] + 1e-3
+    dumped = {p.stem: np.load(p) for p in d_out.glob("*.npy")}
+    assert sorted(dumped) == ["best_params", "eval_mse_log", "params_16bit", "raster"]
+    assert all(v.dtype == np.float32 for v in dumped.values()) and sum(v.nbytes for v in dumped.values()) <= 64 << 20
+    # the last timed tile is tile warmup + steps - 1
+    fit = codec.fit_many([ops.to_device_u16(synthetic_tile(3, 8, 192, 256), dev)], 5, 2, 64, 2, 1e-3, 2048, 3,
+                         cfg=FeatCfg(use_coordinates=False, embedding=False), seed=19920517, in_flight=1)[0]
+    p16 = codec.truncate_device(fit.best_params, 16)
+    rec = ops.from_device_u16(codec.apply_device(fit.geom, fit.net, fit.msb, p16))
+    assert np.array_equal(dumped["best_params"].view(np.uint32), fit.best_params.cpu().numpy().view(np.uint32))
+    assert np.array_equal(dumped["params_16bit"].view(np.uint32), p16.cpu().numpy().view(np.uint32))
+    assert np.array_equal(dumped["eval_mse_log"], fit.mse_log.cpu().numpy())
+    assert np.array_equal(dumped["raster"], rec.reshape(-1).astype(np.float32))
+
+
 def test_bench_four_band_run_has_its_own_roofline(dev):
     """`bench.py --bands 4` (the reference's majority shape) on a small tile: the line names the workload, the fits of the timed
     region equal the lone fit bit for bit, FLOPs are counted over the 96 features the step multiplies."""
@@ -731,7 +767,7 @@ def test_bench_four_band_run_has_its_own_roofline(dev):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bands", "4", "--steps", "4", "--warmup", "2", "--height", "192",
-                          "--width", "256", "-bs", "2048", "-e", "3", "--no-cpu-baseline", "--repeats", "1"],
+                          "--width", "256", "-bs", "2048", "-e", "3", "--no-cpu-baseline", "--repeats", "1", "--full"],
                          check=True, env=env, capture_output=True, text=True, timeout=900).stdout
     d = json.loads([ln for ln in out.splitlines() if ln.strip()][-1])
     assert "4-band" in d["config"]["workload"] and d["timed_equals_lone"] is True and d["config"]["tiles_per_launch"] == 2
