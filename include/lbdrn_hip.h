@@ -107,6 +107,27 @@ size_t lbdrn_forward_workspace(const lbdrn_net *net, int64_t B);
 int lbdrn_forward(const lbdrn_net *net, const float *params, const float *x, int64_t B, float *y,
                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* Autograd of LBDRNModel (LBDRNmodel.py:39-43,79-82): what `loss.backward()` (modified_ignite_engine.py:24) computes for
+ * the network, from an ARBITRARY upstream gradient dy = dL/dy -- the loss, the optimiser and the schedule stay the
+ * caller's.  Same argument checks and batch limit as lbdrn_forward; any shape and either activation (generic kernels).
+ *   lbdrn_tape_bytes          size of the tape for B rows (host arithmetic, no device needed): the hidden outputs
+ *                             [nl][B][bc] and their activation derivatives [nl][B][bc] (cos(30 z) for Sine, 1 / 0 for
+ *                             ReLU), each region 256-byte aligned.
+ *   lbdrn_forward_tape        the forward pass keeping the tape: y[B][C] is lbdrn_forward's output bit for bit.
+ *   lbdrn_backward_workspace  device scratch bytes of lbdrn_backward for B rows (host arithmetic).
+ *   lbdrn_backward            from x, the tape and y of one lbdrn_forward_tape call and dy[B][C]: grads[param_count]
+ *                             (state_dict order, OVERWRITTEN -- accumulation is the caller's) and, where dx is not
+ *                             NULL, dx[B][F] = dL/dx.  The summation tree is lbdrn_train_step's: with dy formed as
+ *                             its MSE gradient, (2 (y - t)) / (B C) in float32, grads equals its grads bit for bit.
+ * A tape or workspace shorter than the sizes above returns LBDRN_E_WORKSPACE. */
+size_t lbdrn_tape_bytes(const lbdrn_net *net, int64_t B);
+int lbdrn_forward_tape(const lbdrn_net *net, const float *params, const float *x, int64_t B, float *y,
+                       void *tape, size_t tape_bytes, void *stream);
+size_t lbdrn_backward_workspace(const lbdrn_net *net, int64_t B);
+int lbdrn_backward(const lbdrn_net *net, const float *params, const float *x, int64_t B, const void *tape,
+                   size_t tape_bytes, const float *y, const float *dy, float *grads, float *dx, void *workspace,
+                   size_t workspace_bytes, void *stream);
+
 /* a2+a5+a11 -- decode.py:73-134 in one pass: features from the MSB plane, forward,
  * r = round_half_even(y*(2^K-1)), out = (msb<<K) + r as uint16 [C][H][W].
  * y_out (optional, may be NULL) receives the sigmoid outputs [H*W][C].

@@ -38,22 +38,27 @@ using namespace lbdrn;
 static int device_ok()
 {
     static thread_local int cached = 1;  // 1 = unknown, 0 = ok, <0 = error
+    static thread_local char why[384] = "";
+    if (cached < 0) set_error("%s", why);   // every failing call says why, not only the first
     if (cached != 1) return cached;
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess || n < 1) {
-        set_error("no HIP device available (%s); liblbdrn_hip has no CPU path",
-                  e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+        snprintf(why, sizeof(why), "no HIP device available (%s); liblbdrn_hip has no CPU path",
+                 e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+        set_error("%s", why);
         return cached = LBDRN_E_DEVICE;
     }
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) {
-        set_error("cannot query the current HIP device");
+        snprintf(why, sizeof(why), "cannot query the current HIP device");
+        set_error("%s", why);
         return cached = LBDRN_E_DEVICE;
     }
     if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0) {
-        set_error("device %d is %s; this library is built for gfx950 (MI355X) only", dev, prop.gcnArchName);
+        snprintf(why, sizeof(why), "device %d is %s; this library is built for gfx950 (MI355X) only", dev, prop.gcnArchName);
+        set_error("%s", why);
         return cached = LBDRN_E_DEVICE;
     }
     return cached = 0;
@@ -133,6 +138,38 @@ int lbdrn_forward(const lbdrn_net* net, const float* params, const float* x, int
     LBDRN_REQUIRE(params && x && y && B >= 0, "null pointer or negative batch");
     NEED_DEVICE();
     return generic_forward(*net, params, x, B, y, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t lbdrn_tape_bytes(const lbdrn_net* net, int64_t B)
+{
+    if (check_net(net) || B < 0) return 0;
+    return generic_tape_bytes(*net, B);
+}
+
+int lbdrn_forward_tape(const lbdrn_net* net, const float* params, const float* x, int64_t B, float* y, void* tape,
+                       size_t tape_bytes, void* stream)
+{
+    if (int rc = check_net(net)) return rc;
+    LBDRN_REQUIRE(params && x && y && B >= 0, "null pointer or negative batch");
+    NEED_DEVICE();
+    return generic_forward_tape(*net, params, x, B, y, tape, tape_bytes, (hipStream_t)stream);
+}
+
+size_t lbdrn_backward_workspace(const lbdrn_net* net, int64_t B)
+{
+    if (check_net(net) || B < 0) return 0;
+    return generic_backward_workspace(*net, B);
+}
+
+int lbdrn_backward(const lbdrn_net* net, const float* params, const float* x, int64_t B, const void* tape,
+                   size_t tape_bytes, const float* y, const float* dy, float* grads, float* dx, void* workspace,
+                   size_t workspace_bytes, void* stream)
+{
+    if (int rc = check_net(net)) return rc;
+    LBDRN_REQUIRE(params && x && y && dy && grads && B >= 0, "null pointer or negative batch");
+    NEED_DEVICE();
+    return generic_backward(*net, params, x, B, tape, tape_bytes, y, dy, grads, dx, workspace, workspace_bytes,
+                            (hipStream_t)stream);
 }
 
 size_t lbdrn_apply_workspace(const lbdrn_geom* g, const lbdrn_net* net)

@@ -75,6 +75,13 @@ size_t generic_train_workspace(const lbdrn_net& net, int B);
 int generic_train_step(const lbdrn_net& net, const float* x, const float* t, int B, float* params,
                        float* m, float* v, int64_t adam_step, double lr, int apply_adam,
                        float* loss, float* grads, void* ws, size_t ws_bytes, hipStream_t s);
+size_t generic_tape_bytes(const lbdrn_net& net, int64_t B);
+size_t generic_backward_workspace(const lbdrn_net& net, int64_t B);
+int generic_forward_tape(const lbdrn_net& net, const float* params, const float* x, int64_t B, float* y, void* tape,
+                         size_t tape_bytes, hipStream_t s);
+int generic_backward(const lbdrn_net& net, const float* params, const float* x, int64_t B, const void* tape,
+                     size_t tape_bytes, const float* y, const float* dy, float* grads, float* dx, void* ws,
+                     size_t ws_bytes, hipStream_t s);
 int generic_train_epoch(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                         const uint16_t* msb, const int64_t* perm, int64_t n, int bs, float* params,
                         float* m, float* v, int64_t step0, double lr, float* losses, void* ws,

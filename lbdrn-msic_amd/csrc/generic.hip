@@ -330,6 +330,20 @@ struct BackDx {
     }
 };
 
+// dx[b][k] = sum_j dz0[b][j] W0[j][k], j ascending: BackDx without the activation factor (autograd of the first
+// nn.Linear with respect to its input)
+struct InputDx {
+    static constexpr bool a_k_contig = true, b_k_contig = false;
+    int M, N, Kd, kchunk;
+    const float* dz;  // [M][Kd]
+    const float* W;   // [Kd][N]
+    float* out;       // [M][N]
+    __device__ float a(int m, int k) const { return dz[(int64_t)m * Kd + k]; }
+    __device__ float b(int k, int n) const { return W[(int64_t)k * N + n]; }
+    __device__ float init(int, int) const { return 0.0f; }
+    __device__ void store(int m, int n, float v, int) const { out[(int64_t)m * N + n] = v; }
+};
+
 // dW[j][k] = sum_b dz[b][j] in[b][k] and, as column N-1 (an input of ones), db[j] = sum_b dz[b][j]
 // (autograd of nn.Linear).  The batch sum is cut into slices of kchunk rows (blockIdx.z); each slice
 // is a b-ordered fmaf chain into part[z][M][N]; k_reduce_slices then adds the slices in z order.
@@ -649,17 +663,64 @@ static size_t carve_train(const lbdrn_net& net, int B, void* ws, TrainWs* w)
 size_t generic_train_workspace(const lbdrn_net& net, int B) { return carve_train(net, B, nullptr, nullptr); }
 
 // gradients of one Linear: gW[rows][cols] and, directly behind it, gb[rows]
-static int grad_layer(const TrainWs& w, int rows, int cols, int B, const float* dz, const float* in,
-                      float* gW, hipStream_t s)
+static int grad_layer(float* slices, int rows, int cols, int B, const float* dz, const float* in, float* gW,
+                      hipStream_t s)
 {
-    GradW g{rows, cols + 1, B, GRAD_SLICE, dz, in, w.slices};
+    GradW g{rows, cols + 1, B, GRAD_SLICE, dz, in, slices};
     if (int rc = launch_gemm(g, s)) return rc;
-    const int slices = (B + GRAD_SLICE - 1) / GRAD_SLICE;
+    const int nsl = (B + GRAD_SLICE - 1) / GRAD_SLICE;
     const int total = rows * (cols + 1);
-    k_reduce_slices<<<(total + 255) / 256, 256, 0, s>>>(w.slices, slices, rows, cols + 1, gW,
-                                                        gW + (int64_t)rows * cols);
+    k_reduce_slices<<<(total + 255) / 256, 256, 0, s>>>(slices, nsl, rows, cols + 1, gW, gW + (int64_t)rows * cols);
     LBDRN_LAUNCH_CHECK();
     return 0;
+}
+
+// forward keeping what the backward needs: h[l] = hidden outputs, dact[l] = their activation derivative (cos(30 z) for
+// Sine, 1 / 0 for ReLU), each [nl][B][bc]; y[B][C] from the launch lbdrn_forward's head runs
+static int forward_keep(const lbdrn_net& net, const float* params, const float* x, int B, float* h, float* dact, float* y,
+                        hipStream_t s)
+{
+    const size_t act = (size_t)B * net.bc;
+    const float* in = x;
+    int nin = net.F;
+    for (int l = 0; l < net.nl; ++l) {
+        const float* W = params + layer_offset(net, l);
+        if (int rc = launch_hidden<true>(net, B, nin, in, W, h + l * act, dact + l * act, s)) return rc;
+        in = h + l * act;
+        nin = net.bc;
+    }
+    const float* Wl = params + layer_offset(net, net.nl);
+    LinearFwd<ACT_SIGMOID, false> g{B, net.C, net.bc, net.bc, in, Wl, Wl + (int64_t)net.C * net.bc, y, nullptr};
+    return launch_gemm(g, s);
+}
+
+// the generic backward, from dzl = dL/dz of the head: every layer's gW / gb into grads (state_dict order), through the
+// hidden layers with BackDx (dz ping-pong [2][B][bc]), and dL/dx[B][F] where dx is not null
+static int backward_from_head(const lbdrn_net& net, const float* params, const float* x, int B, const float* h,
+                              const float* dact, const float* dzl, float* const dz[2], float* slices, float* grads,
+                              float* dx, hipStream_t s)
+{
+    const size_t act = (size_t)B * net.bc;
+    const float* Wl = params + layer_offset(net, net.nl);
+    if (int rc = grad_layer(slices, net.C, net.bc, B, dzl, h + (net.nl - 1) * act, grads + layer_offset(net, net.nl), s))
+        return rc;
+    const float* dz_up = dzl;
+    int n_up = net.C;
+    const float* W_up = Wl;
+    for (int l = net.nl - 1; l >= 0; --l) {
+        float* d = dz[l & 1];
+        BackDx bd{B, net.bc, n_up, n_up, dz_up, W_up, dact + l * act, d, net.act == LBDRN_ACT_RELU};
+        if (int rc = launch_gemm(bd, s)) return rc;
+        const int lin = l ? net.bc : net.F;
+        const float* lin_act = l ? h + (l - 1) * act : x;
+        if (int rc = grad_layer(slices, net.bc, lin, B, d, lin_act, grads + layer_offset(net, l), s)) return rc;
+        dz_up = d;
+        n_up = net.bc;
+        W_up = params + layer_offset(net, l);
+    }
+    if (!dx) return 0;
+    InputDx g{B, net.F, net.bc, net.bc, dz_up, params, dx};
+    return launch_gemm(g, s);
 }
 
 int generic_train_step(const lbdrn_net& net, const float* x, const float* t, int B, float* params,
@@ -674,21 +735,7 @@ int generic_train_step(const lbdrn_net& net, const float* x, const float* t, int
     TrainWs w;
     carve_train(net, B, ws, &w);
     const int64_t NP = param_count(net);
-    const size_t act = (size_t)B * net.bc;
-    // forward, keeping activations and cos(30 z)
-    const float* in = x;
-    int nin = net.F;
-    for (int l = 0; l < net.nl; ++l) {
-        const float* W = params + layer_offset(net, l);
-        if (int rc = launch_hidden<true>(net, B, nin, in, W, w.h + l * act, w.cs + l * act, s)) return rc;
-        in = w.h + l * act;
-        nin = net.bc;
-    }
-    const float* Wl = params + layer_offset(net, net.nl);
-    {
-        LinearFwd<ACT_SIGMOID, false> g{B, net.C, net.bc, net.bc, in, Wl, Wl + (int64_t)net.C * net.bc, w.y, nullptr};
-        if (int rc = launch_gemm(g, s)) return rc;
-    }
+    if (int rc = forward_keep(net, params, x, B, w.h, w.cs, w.y, s)) return rc;
     // loss + d/dz of the last layer
     const int64_t total = (int64_t)B * net.C;
     const float inv = 1.0f / ((float)B * (float)net.C);
@@ -698,28 +745,93 @@ int generic_train_step(const lbdrn_net& net, const float* x, const float* t, int
         k_finish_loss<<<1, 64, 0, s>>>(w.partial, LOSS_BLOCKS, (double)total, loss);
         LBDRN_LAUNCH_CHECK();
     }
-    // last layer gradients
-    float* gl = w.grads + layer_offset(net, net.nl);
-    if (int rc = grad_layer(w, net.C, net.bc, B, w.dzl, w.h + (net.nl - 1) * act, gl, s)) return rc;
-    // back through the hidden layers
-    const float* dz_up = w.dzl;
-    int n_up = net.C;
-    const float* W_up = Wl;
-    for (int l = net.nl - 1; l >= 0; --l) {
-        float* dz = w.dz[l & 1];
-        BackDx bd{B, net.bc, n_up, n_up, dz_up, W_up, w.cs + l * act, dz, net.act == LBDRN_ACT_RELU};
-        if (int rc = launch_gemm(bd, s)) return rc;
-        const int lin = l ? net.bc : net.F;
-        const float* lin_act = l ? w.h + (l - 1) * act : x;
-        float* gW = w.grads + layer_offset(net, l);
-        if (int rc = grad_layer(w, net.bc, lin, B, dz, lin_act, gW, s)) return rc;
-        dz_up = dz;
-        n_up = net.bc;
-        W_up = params + layer_offset(net, l);
-    }
+    if (int rc = backward_from_head(net, params, x, B, w.h, w.cs, w.dzl, w.dz, w.slices, w.grads, nullptr, s)) return rc;
     if (grads_out) LBDRN_HIP_TRY(hipMemcpyAsync(grads_out, w.grads, NP * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (apply_adam) return launch_adam(params, m, v, w.grads, NP, adam_step, lr, s);
     return 0;
+}
+
+// ------------------------------------------------------------------ autograd: forward with tape, backward from dL/dy
+
+// dz[e] = dy[e] * (y (1-y)): sigmoid backward of the head, k_loss_grad's second line without the MSE factor
+__global__ void __launch_bounds__(256)
+    k_head_grad(const float* __restrict__ y, const float* __restrict__ dy, int64_t total, float* __restrict__ dz)
+{
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+        const float yy = y[e];
+        dz[e] = dy[e] * (yy * (1.0f - yy));
+    }
+}
+
+static size_t tape_half(const lbdrn_net& net, int64_t B) { return align_up((size_t)net.nl * B * net.bc * sizeof(float), 256); }
+
+size_t generic_tape_bytes(const lbdrn_net& net, int64_t B) { return 2 * tape_half(net, B); }
+
+// dzl [B][C], dz [2][B][bc], GradW slices [ceil(B/GRAD_SLICE)][max(bc, C)][max(bc, F) + 1]
+static size_t carve_backward(const lbdrn_net& net, int64_t B, void* ws, float** dzl, float** dz, float** slices)
+{
+    char* p = (char*)ws;
+    auto take = [&](size_t bytes) {
+        char* r = p;
+        p += align_up(bytes, 256);
+        return (float*)r;
+    };
+    const size_t nsl = (size_t)(B + GRAD_SLICE - 1) / GRAD_SLICE;
+    const size_t rows = (size_t)std::max(net.bc, net.C), cols = (size_t)std::max(net.bc, net.F) + 1;
+    float* a = take((size_t)B * net.C * sizeof(float));
+    float* d0 = take((size_t)B * net.bc * sizeof(float));
+    float* d1 = take((size_t)B * net.bc * sizeof(float));
+    float* sl = take(nsl * rows * cols * sizeof(float));
+    if (dzl) {
+        *dzl = a;
+        dz[0] = d0;
+        dz[1] = d1;
+        *slices = sl;
+    }
+    return (size_t)(p - (char*)ws);
+}
+
+size_t generic_backward_workspace(const lbdrn_net& net, int64_t B) { return carve_backward(net, B, nullptr, nullptr, nullptr, nullptr); }
+
+int generic_forward_tape(const lbdrn_net& net, const float* params, const float* x, int64_t B, float* y, void* tape,
+                         size_t tape_bytes, hipStream_t s)
+{
+    if (B == 0) return 0;
+    LBDRN_REQUIRE(B < ((int64_t)1 << 31) / std::max(net.bc, net.F), "batch too large for one call");
+    if (!tape || tape_bytes < generic_tape_bytes(net, B)) {
+        set_error("tape too small: %zu < %zu", tape_bytes, generic_tape_bytes(net, B));
+        return LBDRN_E_WORKSPACE;
+    }
+    float* h = (float*)tape;
+    float* dact = (float*)((char*)tape + tape_half(net, B));
+    return forward_keep(net, params, x, (int)B, h, dact, y, s);
+}
+
+int generic_backward(const lbdrn_net& net, const float* params, const float* x, int64_t B, const void* tape,
+                     size_t tape_bytes, const float* y, const float* dy, float* grads, float* dx, void* ws,
+                     size_t ws_bytes, hipStream_t s)
+{
+    if (B == 0) {   // the gradient of an empty batch
+        LBDRN_HIP_TRY(hipMemsetAsync(grads, 0, param_count(net) * sizeof(float), s));
+        return 0;
+    }
+    LBDRN_REQUIRE(B < ((int64_t)1 << 31) / std::max(net.bc, net.F), "batch too large for one call");
+    if (!tape || tape_bytes < generic_tape_bytes(net, B)) {
+        set_error("tape too small: %zu < %zu", tape_bytes, generic_tape_bytes(net, B));
+        return LBDRN_E_WORKSPACE;
+    }
+    if (!ws || ws_bytes < generic_backward_workspace(net, B)) {
+        set_error("backward workspace too small: %zu < %zu", ws_bytes, generic_backward_workspace(net, B));
+        return LBDRN_E_WORKSPACE;
+    }
+    float *dzl, *dz[2], *slices;
+    carve_backward(net, B, ws, &dzl, dz, &slices);
+    const float* h = (const float*)tape;
+    const float* dact = (const float*)((const char*)tape + tape_half(net, B));
+    const int64_t total = B * net.C;
+    k_head_grad<<<(unsigned)std::min<int64_t>((total + 255) / 256, 1024), 256, 0, s>>>(y, dy, total, dzl);
+    LBDRN_LAUNCH_CHECK();
+    return backward_from_head(net, params, x, (int)B, h, dact, dzl, dz, slices, grads, dx, s);
 }
 
 int generic_train_epoch(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,

@@ -52,6 +52,10 @@ SIGNATURES = {
     "lbdrn_features": (ctypes.c_int, [_GP, _vp, _vp, _i64, _vp, _vp]),
     "lbdrn_forward_workspace": (_sz, [_NP, _i64]),
     "lbdrn_forward": (ctypes.c_int, [_NP, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "lbdrn_tape_bytes": (_sz, [_NP, _i64]),
+    "lbdrn_forward_tape": (ctypes.c_int, [_NP, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "lbdrn_backward_workspace": (_sz, [_NP, _i64]),
+    "lbdrn_backward": (ctypes.c_int, [_NP, _vp, _vp, _i64, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "lbdrn_apply_workspace": (_sz, [_GP, _NP]),
     "lbdrn_decode_fused": (ctypes.c_int, [_GP, _NP, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     "lbdrn_eval_sse": (ctypes.c_int, [_GP, _NP, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),

@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .autograd import LBDRNFunction
 
 
 class Sine(nn.Module):
@@ -43,6 +44,19 @@ class SirenLayer(nn.Module):
 
 
 class LBDRNModel(nn.Module):
+    """The reference's LBDRNModel (LBDRNmodel.py:58-82) with its forward in liblbdrn_hip.
+
+    forward() records an autograd graph -- so that the reference's trainer step (modified_ignite_engine.py:18-27:
+    zero_grad, train(), forward, loss, backward(), step) runs on this module -- when all three hold:
+      - grad mode is enabled;
+      - a parameter or x requires grad;
+      - the module was put in training mode by an explicit model.train() (the reference's trainer calls it before every
+        forward); model.eval() turns it off again.
+    The graph's backward is lbdrn_backward (lbdrn_hip.autograd): gradients of every parameter and, when x requires
+    grad, of x, accumulated into .grad by torch.  The parameters must then already be on x's device.  Otherwise (a
+    freshly built module included) the output has no grad_fn, as an inference forward.
+    """
+
     def __init__(self, dim_in, dim_hidden, dim_out=4, num_layers=1, w0=30.0, w0_initial=30.0,
                  use_bias=True, activation=None, final_activation=None):
         super().__init__()
@@ -61,6 +75,15 @@ class LBDRNModel(nn.Module):
         self.hip_act = ops.ACT_RELU if relu else ops.ACT_SINE
         self._fused_ok = ((activation is None and w0 == 30.0 and w0_initial == 30.0 or relu)
                           and final_activation is None and use_bias and num_layers >= 1)
+        self._explicit_train = False   # set by train(): see the class docstring
+
+    def train(self, mode=True):
+        self._explicit_train = bool(mode)
+        return super().train(mode)
+
+    def hip_parameters(self):
+        """The parameters in state_dict order (the order of flat_parameters() and of lbdrn_backward's grads)."""
+        return list(self.state_dict(keep_vars=True).values())
 
     def flat_parameters(self):
         """state_dict order, one float32 vector (ref encode.py:123-128)."""
@@ -76,6 +99,10 @@ class LBDRNModel(nn.Module):
                 "on) and activation=torch.nn.ReLU(); other activations have no HIP kernel")
         if not x.is_cuda:
             raise ops._lib.LbdrnError("LBDRNModel.forward needs a device tensor: this package has no CPU path")
+        if self.training and self._explicit_train and torch.is_grad_enabled():
+            params = self.hip_parameters()
+            if x.requires_grad or any(p.requires_grad for p in params):
+                return LBDRNFunction.apply(self.hip_net(), x, *params)
         flat = self.flat_parameters().to(x.device)
         return ops.forward(self.hip_net(), flat, x)
 

@@ -124,6 +124,40 @@ def forward(net, params, x):
     return y
 
 
+def forward_tape(net, params, x):
+    """forward() keeping what backward() needs -> (y [B,C], tape: a uint8 device buffer).  y equals forward()'s bit for
+    bit.  ref LBDRNmodel.py:79-82 under autograd"""
+    _need_cuda(params, x)
+    x = x.contiguous().float()
+    params = params.contiguous().float()
+    B = x.shape[0]
+    assert x.shape[1] == net.F and params.numel() == param_count(net)
+    y = torch.empty((B, net.C), dtype=torch.float32, device=x.device)
+    nbytes = lib().lbdrn_tape_bytes(ctypes.byref(net), B)
+    tape = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _call(lib().lbdrn_forward_tape, x, ctypes.byref(net), _ptr(params), _ptr(x), B, _ptr(y), _ptr(tape), nbytes)
+    return y, tape
+
+
+def backward(net, params, x, tape, y, dy, want_dx=False):
+    """Gradients from an upstream dL/dy [B,C] and one forward_tape() call's (x, tape, y) -> (grads [param_count] in
+    state_dict order, dL/dx [B,F] or None).  ref modified_ignite_engine.py:24 (loss.backward())"""
+    _need_cuda(params, x, tape, y, dy)
+    x = x.contiguous().float()
+    params = params.contiguous().float()
+    dy = dy.contiguous().float()
+    B = x.shape[0]
+    assert x.shape[1] == net.F and params.numel() == param_count(net)
+    assert y.shape == (B, net.C) and dy.shape == (B, net.C) and y.is_contiguous()
+    grads = torch.empty(param_count(net), dtype=torch.float32, device=x.device)
+    dx = torch.empty((B, net.F), dtype=torch.float32, device=x.device) if want_dx else None
+    nbytes = lib().lbdrn_backward_workspace(ctypes.byref(net), B)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    _call(lib().lbdrn_backward, x, ctypes.byref(net), _ptr(params), _ptr(x), B, _ptr(tape), tape.numel(), _ptr(y),
+          _ptr(dy), _ptr(grads), _ptr(dx), _ptr(ws), nbytes)
+    return grads, dx
+
+
 class ApplyWorkspace:
     def __init__(self, geom, net, device):
         self.nbytes = lib().lbdrn_apply_workspace(ctypes.byref(geom.c), ctypes.byref(net))
