@@ -867,6 +867,11 @@ static int run_apply(const lbdrn_geom& g, const lbdrn_net& net, int mode, const 
                      double* sse, void* ws, size_t ws_bytes, bool background, hipStream_t s)
 {
     ApplyArgs A;
+    if (mode == MODE_EVAL_X16) {   // (a hint: where the x16 weight pack does not fit in LDS, or fits only at a shorter tile than the fast
+                                   //  plan's -- C = 8, D = 3, bc = 64 --, the pass is the fast one)
+        ApplyPlan fp, xp;
+        if (make_plan(g, net, &fp, true, false) && (!make_plan(g, net, &xp, true, true) || xp.TH < fp.TH)) mode = MODE_EVAL_FAST;
+    }
     if (!make_plan(g, net, &A.p, mode_fast(mode), mode == MODE_EVAL_X16))   // too wide for LDS-resident weights: the streaming kernel (apply_wide.inc)
         return run_wapply(g, net, mode, img, msb, params, out, y_out, sse, ws, ws_bytes, background, s);
     if (mode == MODE_EVAL_X16 && !A.p.x16) mode = MODE_EVAL_FAST;    // (a hint: the shape or the image does not qualify, the pass is the fast one)

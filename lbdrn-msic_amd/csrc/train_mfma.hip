@@ -155,6 +155,9 @@ static int train_kernel_choice()
 }
 
 __host__ __device__ constexpr int stream_rp(int LQ);
+// the layer-0 quarter length of the one shape above 256 features that has a fused step (nl = 2; 256 < Fe <= 384): it runs
+// on k_train_split only -- neither k_train_stream's LDS map nor the tile kernel's fits it --, alone or in a group
+constexpr int SPLIT_WIDE_LQ = 96;
 struct StreamLds;
 static int stream_lds_total(int LQ, int NL);
 
@@ -171,7 +174,9 @@ static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan
         p.fm = centre_skipping_map(g, net);
         for (int lq : {16, 24, 32, 48, 52, 64})   // (24: the reference's 4-band shape -- F = 100, 96 features that can differ from zero)
             if (p.fm.Fe <= 4 * lq) { p.LQ = lq; break; }
-        if (!p.LQ || (size_t)stream_lds_total(p.LQ, net.nl) * 4 > 160 * 1024) { kind = 0; p.LQ = 0; p.fm = FeatMap{net.F, 0, 0, 0}; }
+        // 256 < Fe <= 384 at nl = 2 (D = 3 windows on 6..8 bands): k_train_split alone, with W_0 in a ring (train_split.inc)
+        if (!p.LQ && net.nl == 2 && p.fm.Fe <= 4 * SPLIT_WIDE_LQ) p.LQ = SPLIT_WIDE_LQ;
+        if (!p.LQ || (p.LQ != SPLIT_WIDE_LQ && (size_t)stream_lds_total(p.LQ, net.nl) * 4 > 160 * 1024)) { kind = 0; p.LQ = 0; p.fm = FeatMap{net.F, 0, 0, 0}; }
     }
     if (kind != 2 && net.act != LBDRN_ACT_SINE) return false;
     if (kind != 2)
@@ -179,7 +184,7 @@ static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan
             if (net.F <= 4 * lq && p.RP <= 4 * lq + 4) { p.LQ = lq; break; }
     if (!p.LQ) return false;
     p.XP = 4 * p.LQ + 4;
-    p.NT0 = (p.fm.Fe + 15) / 16;
+    p.NT0 = p.LQ == SPLIT_WIDE_LQ ? SPLIT_WIDE_LQ / 4 : (p.fm.Fe + 15) / 16;   // (the wide step's one instance: 24 strips, the slots past Fe zero)
     if (kind != 2 && 16 * p.NT0 > p.XP) return false;
     p.NP = param_count(net);
     int64_t o = 0;
@@ -201,7 +206,7 @@ static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan
     p.wave_lds_floats = 0;
     if (kind == 2) {
         p.RP = stream_rp(p.LQ);   // the matrix in the order layer 0 eats it (train_stream.inc)
-        p.wave_lds_floats = stream_lds_total(p.LQ, net.nl);
+        p.wave_lds_floats = p.LQ == SPLIT_WIDE_LQ ? 0 : stream_lds_total(p.LQ, net.nl);
     }
     p.wave = kind;
     int s = 4 * p.NT0 * 256;
@@ -1300,8 +1305,11 @@ static int dispatch_stream(const TrainArgs& A, int nwg, int count, hipStream_t s
 // the 4-band shape of the reference's own image list (run.sh:14-28)
 static bool split_available(const TrainPlan& p, const lbdrn_net& net)
 {
-    return p.wave == 2 && net.nl == 2 && ((p.LQ == 48 && p.NT0 == 12) || (p.LQ == 64 && p.NT0 == 16) || (p.LQ == 24 && p.NT0 == 6));
+    return p.wave == 2 && net.nl == 2 && ((p.LQ == 48 && p.NT0 == 12) || (p.LQ == 64 && p.NT0 == 16) || (p.LQ == 24 && p.NT0 == 6) ||
+                                          (p.LQ == SPLIT_WIDE_LQ && p.NT0 == SPLIT_WIDE_LQ / 4));
 }
+// ... and the wide shape has nothing else: every step of it, alone or in a group, one row or many, is k_train_split's
+static bool split_only(const TrainPlan& p) { return p.LQ == SPLIT_WIDE_LQ; }
 
 template <int LQ, int NT0C, int ACT>
 static int launch_split_act(const TrainArgs& A, int nwg, int count, hipStream_t s)
@@ -1324,6 +1332,7 @@ static int launch_split(const TrainArgs& A, int nwg, int count, hipStream_t s)
 
 static int dispatch_split(const TrainArgs& A, int nwg, int count, hipStream_t s)
 {
+    if (A.p.LQ == SPLIT_WIDE_LQ) return launch_split<SPLIT_WIDE_LQ, SPLIT_WIDE_LQ / 4>(A, nwg, count, s);
     return A.p.LQ == 48 ? launch_split<48, 12>(A, nwg, count, s) : A.p.LQ == 24 ? launch_split<24, 6>(A, nwg, count, s) : launch_split<64, 16>(A, nwg, count, s);
 }
 
@@ -1459,12 +1468,12 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
     // A fit that has the device to itself (LBDRN_TRAIN_ALONE) steps on k_train_split where the shape has it: 256 workgroups
     // of 32 rows, every CU, two slabs per 64-row group.  The numbers are k_train_stream's bit for bit (train_split.inc).
 #ifdef LBDRN_EXP_NO_SPLIT   // (A/B build: the lone fit stays on k_train_stream)
-    const bool split = false;
+    const bool split = split_only(A.p);
 #else
 #ifdef LBDRN_EXP_SPLIT_ALIAS_LDS   // (timing only: every launch on k_train_split, groups included -- two workgroups per CU)
     const bool split = split_available(A.p, net);
 #else
-    const bool split = alone && count == 1 && split_available(A.p, net);
+    const bool split = (alone && count == 1 && split_available(A.p, net)) || split_only(A.p);
 #endif
 #endif
     const int red_blocks = A.p.slab_floats / (4 * RED_LANES);
@@ -1513,8 +1522,9 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
         A.next_n = (int)nextB;
         A.touch_row_bytes = (alone && count == 1) ? touch_alone : 0;   // (LBDRN_TRAIN_ALONE; see k_train_stream's loader wave)
         // (split: nwg counts the 64-row GROUPS -- the unit k_reduce_adam adds in its fixed order --, two workgroups each)
-        const bool split_now = split && B >= 2;   // (k_train_split fetches the pixel indices two at a time: a minibatch of ONE row -- the tail of an
-                                                  // epoch of n = 1 (mod batch size) rows -- steps on k_train_stream; the same bits)
+        const bool split_now = split && (B >= 2 || split_only(A.p));   // (k_train_split fetches the pixel indices two at a time: a minibatch of ONE
+                                                  // row -- the tail of an epoch of n = 1 (mod batch size) rows -- steps on k_train_stream; the same bits.
+                                                  // The wide shape's instance fetches them one at a time.)
         auto train_launch = [&]() { return split_now ? dispatch_split(A, 2 * nwg, count, s) : dispatch_train(A, nwg, count, s); };
         if (int rc = train_launch()) return rc;
         if (g_prof_mode == 2)   // measurement only: the same launch again (it writes the same slabs and loss partials)

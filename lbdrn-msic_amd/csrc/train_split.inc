@@ -35,6 +35,19 @@ constexpr int SP_OP = 20;           // [sample][16 channel slots] pitch of dz_ou
 constexpr int SP_PT = 36;           // [unit][32 samples] pitch of the transposed dz copies
 constexpr int SP_SM = 40;           // 1 KB blocks of the small matrices: W_1 [16] | W_1^T [16] | W_last [4] | W_last^T [4]
 
+// The wide-window shape: LQ = 96, 384 features (D = 3 windows on 8 bands with relative colours; 6 and 7 bands pad to it).
+// All 24 W_0 fragment groups (96 KB) and the rows (51 KB) do not fit beside each other, so W_0 passes through a RING of
+// SP_RING groups (48 KB), two halves of SP_RING / 2 groups each: quarter Q of W_0 (groups 6 Q .. 6 Q + 5) lands in half
+// Q mod 2.  Quarters 0 and 1 land with the rows; quarter 2 is requested once every wave is past group 5 (a barrier at the
+// top of layer 0's iteration 7: a wave's MFMAs of group g, which wait for its reads of group g, issue in iteration g + 1),
+// quarter 3 once every wave is past group 11 (iteration 13); each is waited for where its first group is read (12, 18).
+// The rows stay resident for dW_0.  The arithmetic is k_train_split's, unchanged: only where W_0 sits differs.
+constexpr int SP_RING = 12;
+__host__ __device__ constexpr bool split_ring(int LQ) { return LQ > 64; }
+__host__ __device__ constexpr int split_w0_groups(int LQ) { return split_ring(LQ) ? SP_RING : LQ / 4; }   // W_0 groups resident at once
+// small-matrix requests a wave has issued by the end of layer 0's iteration k (SPI per iteration from iteration 1 on)
+__host__ __device__ constexpr int split_small_through(int k, int SPI) { return k * SPI < SP_SM / 4 ? k * SPI : SP_SM / 4; }
+
 // LDS map (floats).  W_0 fragments [G0 groups][4 tiles][256] -- dead behind the barrier after layer 0, where H_1, the dz_1
 // exchange, dz_out and both dz^T move in --; the small matrices; the rows X' [2 sample tiles][G0 + 1 groups][260] as the
 // requests land them (lane-linear 1 KB pieces, group g 4 banks on; the labels are the last group); H_0; the partials.
@@ -42,10 +55,10 @@ struct SplitLds { int w0, sm, x, xt, h0, red, idx, bias, h1, e, zo, zt, total; }
 __host__ __device__ constexpr SplitLds split_lds(int LQ)
 {
     SplitLds L{};
-    const int G0 = LQ / 4;
+    const int G0 = LQ / 4, RG = split_w0_groups(LQ);
     int o = 0;
     const int over = 2 * SPB * SP_HP + SPB * SP_OP + 2 * 64 * SP_PT;   // what moves in over the W_0 fragments behind layer 0
-    L.w0 = o; o += G0 * 4 * 256 > over ? G0 * 4 * 256 : over;         // (LQ < 40: the region is as large as its second life needs it)
+    L.w0 = o; o += RG * 4 * 256 > over ? RG * 4 * 256 : over;         // (LQ < 40: the region is as large as its second life needs it)
 #ifdef LBDRN_EXP_SPLIT_ALIAS_LDS   // (timing only, results garbage: the small matrices and the rows land ON the W_0 fragments, so that the
                                    //  workgroup takes 63 KB and TWO are resident per CU -- what would two waves per SIMD buy this step?)
     L.sm = L.w0;
@@ -106,10 +119,14 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
     static_assert(L.total > 0 && L.total * 4 <= 160 * 1024, "LDS map does not fit");
     static_assert(16 * NT0C == 4 * LQ && G0 >= 4, "the first layer's strips fill its slots");
     // strips w, w + 4, .. (NFS per wave) against all four unit tiles, then REM left-over strips, tile w of each (LQ = 24: 1 + 2)
-    constexpr int NFS = NT0C / 4, REM = NT0C % 4, NIT = NFS + REM, GA = G0 / 2;      // groups 0 .. GA-1 land first
+    constexpr int NFS = NT0C / 4, REM = NT0C % 4, NIT = NFS + REM, GA = split_w0_groups(LQ) / 2;   // groups 0 .. GA-1 land first
     static_assert(NFS >= 1 && REM <= 2, "strip counts of the shapes this is instantiated for");
     // small-matrix requests per MFMA group of layer 0 (its G0 - 1 loop iterations carry SP_SM / 4 of them per wave)
     constexpr int SPI = (SP_SM / 4 + G0 - 2) / (G0 - 1);
+    // the W_0 ring (SP_RING): RG groups resident, quarters of HR groups; without it W_0 lands whole, in two halves
+    constexpr bool RING = split_ring(LQ);
+    constexpr int RG = split_w0_groups(LQ), HR = RG / 2, W0B = RG - GA;   // W0B: groups of the first landing's second phase
+    static_assert(!RING || (G0 == 2 * RG && GA == HR), "the ring holds half of W_0, its quarters land one behind the other");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int st = wv >> 1, uh = wv & 1;            // sample tile, unit half
@@ -158,7 +175,11 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
         long long c0 = p.offB[0], c1 = p.offB[1], c2 = p.offB[2], c3 = A.npix;
         asm volatile("" ::"s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(b0), "s"(b1), "s"(b2), "s"(b3), "s"(b4), "s"(b5), "s"(c0), "s"(c1), "s"(c2), "s"(c3));
     }
-    {   // 64 indices = 512 B: lane l < 32 fetches elements 2 l, 2 l + 1 of the group -- or the minibatch's last two, past its
+    if constexpr (RING) {   // 64 indices, the low 4 bytes of each (pixel indices are < 2^31): lane l fetches element l of the group
+                            // -- or the minibatch's last one, past its end: any minibatch size, one row included
+        const int64_t* isrc = F.perm + min(grp * WB + lane, A.batch_n - 1);
+        stream_dma_dword(reinterpret_cast<const float*>(isrc), lds0 + 4u * (unsigned)(L.idx + 256 * wv));
+    } else {   // 64 indices = 512 B: lane l < 32 fetches elements 2 l, 2 l + 1 of the group -- or the minibatch's last two, past its
         // end (the host launches this kernel on minibatches of two rows or more) --, lanes 32 .. 63 repeat them into the
         // second half of the request's 1 KB
         const int64_t* isrc = F.perm + min(grp * WB + 2 * (lane & 31), A.batch_n - 2);
@@ -178,12 +199,14 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
 #endif
 #pragma unroll
         for (int g = g_lo; g < g_hi; ++g)
-            stream_dma(fsrc + p.pk_w0 + 256 * (wv * G0 + g), lds0 + 4u * (unsigned)(L.w0 + (g * 4 + wv) * 256));
+            stream_dma(fsrc + p.pk_w0 + 256 * (wv * G0 + g), lds0 + 4u * (unsigned)(L.w0 + ((g % RG) * 4 + wv) * 256));
     };
     w0_requests(0, GA);
     stream_wait_vm<GA + 1>();  // the indices have landed (behind them: the biases and W_0 A)
     int64_t raw;
-    {   // this lane's row of the minibatch (rows past the end of a short one repeat its last row: finite values, masked out
+    if constexpr (RING) {
+        raw = reinterpret_cast<const int*>(lds + L.idx + 256 * wv)[min(grow, A.batch_n - 1) - grp * WB];
+    } else {   // this lane's row of the minibatch (rows past the end of a short one repeat its last row: finite values, masked out
         // of the loss) and where the request above put its index
         const int g = min(grow, A.batch_n - 1), l = (g - grp * WB) >> 1;
         const int pos = 2 * l + (g - min(grp * WB + 2 * l, A.batch_n - 2));
@@ -199,7 +222,7 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
             if ((g & 1) == uh) stream_dma(rsrc + 16 * g, lds0 + 4u * (unsigned)(L.x + st * L.xt + g * SGP));
     };
     row_requests(0, GA);
-    w0_requests(GA, G0);
+    w0_requests(GA, RG);
     row_requests(GA, NGR);
     // the small matrices (packed W_1 | W_last | W_1^T | W_last^T -> LDS W_1 | W_1^T | W_last | W_last^T) are not needed before
     // layer 0 is over and go out one per MFMA group of it: pushed out here, behind 25 KB per wave of requests that are, they
@@ -222,7 +245,7 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
     STAMP(1);
     // requests of this wave behind the last one of phase A: W_0 B (G0 - GA) + rows B; behind phase B: the small ones issued by then
     constexpr int ROWS_B0 = split_row_requests(GA, NGR, 0), ROWS_B1 = split_row_requests(GA, NGR, 1);
-    if (uh == 0) stream_wait_vm<G0 - GA + ROWS_B0>(); else stream_wait_vm<G0 - GA + ROWS_B1>();
+    if (uh == 0) stream_wait_vm<W0B + ROWS_B0>(); else stream_wait_vm<W0B + ROWS_B1>();
     stream_barrier();          // phase A has landed: groups 0 .. GA - 1 of W_0 and of both tiles' rows
     STAMP(2);
 
@@ -248,8 +271,8 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
         const float* xbase = Xs + st * L.xt + (4 * split_slot(i) + q) * 4;
         float4 aq[2][2], bq[2];
         auto reads = [&](int g) {
-            aq[g & 1][0] = *reinterpret_cast<const float4*>(wbase + g * 1024);
-            aq[g & 1][1] = *reinterpret_cast<const float4*>(wbase + g * 1024 + 256);
+            aq[g & 1][0] = *reinterpret_cast<const float4*>(wbase + (g % RG) * 1024);
+            aq[g & 1][1] = *reinterpret_cast<const float4*>(wbase + (g % RG) * 1024 + 256);
             bq[g & 1] = *reinterpret_cast<const float4*>(xbase + g * SGP);
         };
         auto mfmas = [&](int g) {
@@ -264,6 +287,22 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
             if (g == GA) {     // the rest of W_0 and of the rows (behind them: the small-matrix requests of the iterations so far)
                 stream_wait_vm<((GA - 1) * SPI < SP_SM / 4 ? (GA - 1) * SPI : SP_SM / 4)>();
                 stream_barrier();
+            }
+            if constexpr (RING) {
+                if (g == GA + 1 || g == 2 * HR + 1) {   // every wave is past group g - 2: its half of the ring takes the next quarter
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    stream_barrier();
+                    const int q0 = g == GA + 1 ? 2 * HR : 3 * HR;
+                    w0_requests(q0, q0 + HR);
+                }
+                if (g == 2 * HR) {   // quarter 2 has landed (behind it: the small-matrix requests of iterations GA + 1 .. g - 1)
+                    stream_wait_vm<split_small_through(2 * HR - 1, SPI) - split_small_through(GA, SPI)>();
+                    stream_barrier();
+                }
+                if (g == 3 * HR) {   // quarter 3 has landed
+                    stream_wait_vm<split_small_through(3 * HR - 1, SPI) - split_small_through(2 * HR, SPI)>();
+                    stream_barrier();
+                }
             }
 #pragma unroll
             for (int b = (g - 1) * SPI; b < g * SPI; ++b)

@@ -173,7 +173,10 @@ def default_in_flight(C, H, W, K, D, base_channel, num_layers, cfg=None, path=No
       workgroups per CU), k_dw_wide (66 KB, 284 registers: one wave per SIMD), k_reduce_adam / the evaluation pass.  Three
       chains can each have one of them resident; a fourth chain's forward/backward workgroups queue behind the resident pair
       and which chains meet decides the time (343 or 386 ms per tile: DESIGN 4.5): 3 fits;
-    * the generic path is many small launches per step: 4."""
+    * the generic path is many small launches per step: 4.
+    The wide bc = 64 step (D = 3 on 6..8 bands) is one k_train_split launch of 256 workgroups of 156 KB per fit
+    and minibatch, groups included: the reduce / Adam launch (4 KB) still fits beside it, and 4 in flight as pairs measured
+    123 ms per tile against 157 alone (profiles/wide_window_timing.txt)."""
     cfg = cfg or FeatCfg.from_constants()
     if path == ops._lib.PATH_GENERIC:
         return 4
