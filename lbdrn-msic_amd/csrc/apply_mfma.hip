@@ -30,9 +30,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-#ifndef LBDRN_APPLY_CHUNK
-#define LBDRN_APPLY_CHUNK 20   // layer-0 steps whose B operands are made in one go, a multiple of 4 (0: four at a time, round
-#endif                         // 2's loop); eval pass on the 8 x 2048^2 tile: 1.845 ms at 0, 1.79-1.82 at 20, 1.87 at 52
+constexpr int APPLY_CHUNK = 20;   // layer-0 steps whose B operands are made in one go, a multiple of 4; eval pass on the
+                                  // 8 x 2048^2 tile: 1.79-1.82 ms at 20, 1.87 at 52, 1.845 with none (round 2's loop: four at a time)
 constexpr int APPLY_WAVES = 8;
 constexpr int APPLY_THREADS = APPLY_WAVES * 64;
 constexpr int TILE_W = 64;
@@ -83,14 +82,9 @@ static bool make_plan(const lbdrn_geom& g, const lbdrn_net& net, ApplyPlan* p, b
     q.S0 = g.P + ((q.ncolor + 1) / 2 + 3) / 4 * 4;
     // the evaluation pass in the tolerance arithmetic may take the features in any order (the sum is held to 1e-6, not to
     // a bit pattern): channel pairs, and no step for the window centres, which are exact zeros with RELATIVE
-    // (LBDRNdataset.py:126-128) -- 96 MFMA steps instead of 100 at the headline shape.  (-DLBDRN_EXP_EVAL_NOPAIR: A/B build)
-#ifdef LBDRN_EXP_EVAL_NOPAIR
-    constexpr bool nopair = true;
-#else
-    constexpr bool nopair = false;
-#endif
+    // (LBDRNdataset.py:126-128) -- 96 MFMA steps instead of 100 at the headline shape.
     const int side = 2 * g.D + 1;
-    q.pair = fast && !nopair && q.NT <= 2 && g.use_colors && g.D >= 1 && g.D <= 3 && (g.C % 2) == 0 && q.ncolor == g.C * side * side;
+    q.pair = fast && q.NT <= 2 && g.use_colors && g.D >= 1 && g.D <= 3 && (g.C % 2) == 0 && q.ncolor == g.C * side * side;
     // (NT = 4, bc = 128: the pair's 24 operands on top of 128 accumulator / activation registers would spill at two waves per SIMD)
     q.RS = side * side - ((g.relative && g.D > 0) ? 1 : 0);
     if (q.pair) q.S0 = g.P + (g.C / 2) * q.RS;
@@ -583,57 +577,53 @@ __global__ void __launch_bounds__(APPLY_THREADS) k_apply_mfma(ApplyArgs A)
                 }
             }
             if (!paired) {
-#if LBDRN_APPLY_CHUNK > 0
-            // colour features in chunks of CH steps: the chunk's B operands (window gather, minus centre) are all made
-            // first -- vector and LDS work only --, then its 2 CH MFMAs run with nothing but their A-operand reads
-            // between them: an f32 MFMA and vector work of the SAME wave never overlap, those of the two waves
-            // sharing a SIMD do once their streams are not both a fine mix of the two (scripts/pipe_probe.hip)
-            constexpr int CH = LBDRN_APPLY_CHUNK;
-            static_assert(CH % 4 == 0, "the steps left behind the chunks are taken four at a time");
-            int s4 = P;
-            for (; s4 + CH <= p.S0; s4 += CH) {
-                float bq[CH];
+                // colour features in chunks of CH steps: the chunk's B operands (window gather, minus centre) are all made
+                // first -- vector and LDS work only --, then its 2 CH MFMAs run with nothing but their A-operand reads
+                // between them: an f32 MFMA and vector work of the SAME wave never overlap, those of the two waves
+                // sharing a SIMD do once their streams are not both a fine mix of the two (scripts/pipe_probe.hip)
+                constexpr int CH = APPLY_CHUNK;
+                static_assert(CH % 4 == 0, "the steps left behind the chunks are taken four at a time");
+                int s4 = P;
+                for (; s4 + CH <= p.S0; s4 += CH) {
+                    float bq[CH];
 #pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const int kk = 2 * (s4 + u - P) + h;
-                    const int2 e = *reinterpret_cast<const int2*>(ktab + 2 * kk);
-                    const float nb = tile[pixbase + e.x];
-                    const float ct = tile[pixbase + e.y];
-                    bq[u] = rel ? nb - ct : nb;  // minus centre, LBDRNdataset.py:126-128
+                    for (int u = 0; u < CH; ++u) {
+                        const int kk = 2 * (s4 + u - P) + h;
+                        const int2 e = *reinterpret_cast<const int2*>(ktab + 2 * kk);
+                        const float nb = tile[pixbase + e.x];
+                        const float ct = tile[pixbase + e.y];
+                        bq[u] = rel ? nb - ct : nb;  // minus centre, LBDRNdataset.py:126-128
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int u = 0; u < CH; ++u) {
+                        float a[NT];
+                        load_a<NT>(w0, (s4 + u) * 64 + lane, a);
+#pragma unroll
+                        for (int tt = 0; tt < NT; ++tt)
+                            acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tt], bq[u], acc[tt], 0, 0, 0);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-                __builtin_amdgcn_sched_barrier(0);
+                for (; s4 < p.S0; s4 += 4) {  // the colour features left behind the chunks, four MFMA steps per trip
+                    float bq[4];
+                    float aq[4][NT];
 #pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    float a[NT];
-                    load_a<NT>(w0, (s4 + u) * 64 + lane, a);
+                    for (int u = 0; u < 4; ++u) {
+                        int kk = 2 * (s4 + u - P) + h;
+                        int2 e = *reinterpret_cast<const int2*>(ktab + 2 * kk);
+                        float nb = tile[pixbase + e.x];
+                        float ct = tile[pixbase + e.y];
+                        bq[u] = rel ? nb - ct : nb;  // minus centre, LBDRNdataset.py:126-128
+                        load_a<NT>(w0, (s4 + u) * 64 + lane, aq[u]);
+                    }
 #pragma unroll
-                    for (int tt = 0; tt < NT; ++tt)
-                        acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[tt], bq[u], acc[tt], 0, 0, 0);
+                    for (int u = 0; u < 4; ++u)
+#pragma unroll
+                        for (int tt = 0; tt < NT; ++tt)
+                            acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[u][tt], bq[u], acc[tt], 0, 0, 0);
                 }
-                __builtin_amdgcn_sched_barrier(0);
             }
-            for (; s4 < p.S0; s4 += 4) {
-#else
-            for (int s4 = P; s4 < p.S0; s4 += 4) {  // colour features, four MFMA steps per trip
-#endif
-                float bq[4];
-                float aq[4][NT];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    int kk = 2 * (s4 + u - P) + h;
-                    int2 e = *reinterpret_cast<const int2*>(ktab + 2 * kk);
-                    float nb = tile[pixbase + e.x];
-                    float ct = tile[pixbase + e.y];
-                    bq[u] = rel ? nb - ct : nb;  // minus centre, LBDRNdataset.py:126-128
-                    load_a<NT>(w0, (s4 + u) * 64 + lane, aq[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int tt = 0; tt < NT; ++tt)
-                        acc[tt] = __builtin_amdgcn_mfma_f32_32x32x2f32(aq[u][tt], bq[u], acc[tt], 0, 0, 0);
-            }
-            }   // !paired
             ASTAMP(1);  // layer 0
 #pragma unroll
             for (int tt = 0; tt < NT; ++tt)

@@ -53,14 +53,9 @@ static bool make_wapply_plan(const lbdrn_geom& g, const lbdrn_net& net, WApplyPl
     if (q.ncolor < 0) return false;
     // the evaluation pass in the tolerance arithmetic leaves the always-zero window centres out (LBDRNdataset.py:126-128;
     // its sum is held to 1e-6, not to a bit pattern): F = 200 -> 192 = twelve groups of 16 instead of the fourteen that
-    // 200 pads to.  (-DLBDRN_EXP_EVAL_NOPAIR: A/B build)
-#ifdef LBDRN_EXP_EVAL_NOPAIR
-    constexpr bool noskip = true;
-#else
-    constexpr bool noskip = false;
-#endif
+    // 200 pads to.
     q.S2 = (2 * g.D + 1) * (2 * g.D + 1);
-    q.skip = fast && !noskip && g.use_colors && g.relative && g.D > 0 && q.ncolor == g.C * q.S2;
+    q.skip = fast && g.use_colors && g.relative && g.D > 0 && q.ncolor == g.C * q.S2;
     q.Fe = q.skip ? net.F - g.C : net.F;
     q.G0 = ((q.Fe + 15) / 16 + 1) & ~1;   // even: the kernel walks the groups in pairs (a padding group carries zero weights)
     if (q.ncolor < 1) return false;        // (USE_COLORS off: the generic kernels)
@@ -318,11 +313,7 @@ __global__ void __launch_bounds__(WA_THREADS, 1) k_apply_wide(WApplyArgs A)
 #pragma unroll
                     for (int tt = 0; tt < NT; ++tt) {
 #pragma unroll
-#ifdef LBDRN_EXP_APPLY_NOSIN   // (timing only: the activations cost one multiply -- what do the sines' issue cycles cost the pass?)
-                        for (int r = 0; r < 4; ++r) h[tt][r] = 30.0f * acc[tt][r];
-#else
                         for (int r = 0; r < 4; ++r) h[tt][r] = MODE == MODE_EVAL_FAST ? fast_sin(30.0f * acc[tt][r]) : siren_act(acc[tt][r]);
-#endif
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 };

@@ -338,10 +338,7 @@ __global__ void __launch_bounds__(256)
 // pair index, so that a walk is one 8-byte load per entry), then for every position the predecessors of its list's steps
 // (pred[step]) and the latest step below it (last[position]).  Lists up to LINK_REG entries are ordered in registers,
 // longer ones (the far end of the array: ~ln n entries) in a per-thread strip of LDS.
-#ifndef LBDRN_LINK_LDS
-#define LBDRN_LINK_LDS 24
-#endif
-constexpr int LINK_LDS = LBDRN_LINK_LDS;   // entries of a thread's LDS strip; longer lists (a handful per permutation) re-walk
+constexpr int LINK_LDS = 24;   // entries of a thread's LDS strip; longer lists (a handful per permutation) re-walk
 constexpr int LINK_THREADS = 512;   // the walks are chains of dependent loads: sixteen waves per CU keep more of them in flight
                                     // (256 threads: 204 us per launch, 512: 141; 1024 with strips of 12 entries: 206)
 __global__ void __launch_bounds__(LINK_THREADS)
@@ -463,11 +460,7 @@ struct PermWs {
 };
 static bool perm_partitioned(int64_t n)
 {
-#ifdef LBDRN_EXP_RANDPERM_ATOMIC   // (A/B build: the memory-side atomic path for every n)
-    return false;
-#else
     return n > 16 * PART_SIZE && n <= PART_MAX_N;
-#endif
 }
 
 static int carve_perm(int64_t n, int count, void* ws, PermWs* w)
@@ -532,36 +525,21 @@ int randperm_batch(const uint64_t* seeds, int count, int64_t n, int64_t* out, vo
     const uint32_t un = (uint32_t)n, steps = un - 1;
     SeedList sl;
     for (int c = 0; c < 32; ++c) sl.s[c] = c < count ? (uint32_t)(seeds[c] & 0xffffffffu) : 0u;
-    // timing-only builds (never the shipped library: the permutations are then garbage; the training kernels clamp what
-    // they read): -DLBDRN_EXP_RANDPERM_DIAG=1 no MT19937 launch, =2 none of the launches behind it, =3 neither
-#ifdef LBDRN_EXP_RANDPERM_DIAG
-    constexpr int diag = LBDRN_EXP_RANDPERM_DIAG;
-#else
-    constexpr int diag = 0;
-#endif
-#ifdef LBDRN_EXP_RANDPERM_NOJUMP   // (A/B build: one wave per permutation from end to end)
-    constexpr bool no_jump = true;
-#else
-    constexpr bool no_jump = false;
-#endif
-    const int nseg = no_jump ? 1 : (int)std::min<uint32_t>(MT_MAX_SEG, (steps + MT_SEG - 1) / MT_SEG);
+    const int nseg = (int)std::min<uint32_t>(MT_MAX_SEG, (steps + MT_SEG - 1) / MT_SEG);
     const size_t jstride = w.arr / sizeof(uint32_t);
-    if (!(diag & 1)) {
-        if (nseg > 1) {
-            const uint32_t* polys = nullptr;
-            if (int rc = mt_jump_table_device(&polys)) return rc;
-            k_mt19937_raw<<<dim3(count, 1), 64, 0, s>>>(sl, un, w.j, jstride, MtPlan{0u, MT_PREFIX, nullptr, w.x0});
-            LBDRN_LAUNCH_CHECK();
-            LBDRN_HIP_TRY(hipMemsetAsync(w.win, 0, (size_t)count * (MT_MAX_SEG - 1) * MT_N * sizeof(uint32_t), s));
-            k_mt_jump<<<dim3(nseg - 1, count, JUMP_SPLIT), JUMP_THREADS, 0, s>>>(w.x0, w.j, jstride, polys, w.win);
-            LBDRN_LAUNCH_CHECK();
-            k_mt19937_raw<<<dim3(count, nseg), 64, 0, s>>>(sl, un, w.j, jstride, MtPlan{MT_SEG, 0xffffffffu, w.win, nullptr});
-        } else {
-            k_mt19937_raw<<<dim3(count, 1), 64, 0, s>>>(sl, un, w.j, jstride, MtPlan{0u, 0xffffffffu, nullptr, nullptr});
-        }
+    if (nseg > 1) {
+        const uint32_t* polys = nullptr;
+        if (int rc = mt_jump_table_device(&polys)) return rc;
+        k_mt19937_raw<<<dim3(count, 1), 64, 0, s>>>(sl, un, w.j, jstride, MtPlan{0u, MT_PREFIX, nullptr, w.x0});
         LBDRN_LAUNCH_CHECK();
+        LBDRN_HIP_TRY(hipMemsetAsync(w.win, 0, (size_t)count * (MT_MAX_SEG - 1) * MT_N * sizeof(uint32_t), s));
+        k_mt_jump<<<dim3(nseg - 1, count, JUMP_SPLIT), JUMP_THREADS, 0, s>>>(w.x0, w.j, jstride, polys, w.win);
+        LBDRN_LAUNCH_CHECK();
+        k_mt19937_raw<<<dim3(count, nseg), 64, 0, s>>>(sl, un, w.j, jstride, MtPlan{MT_SEG, 0xffffffffu, w.win, nullptr});
+    } else {
+        k_mt19937_raw<<<dim3(count, 1), 64, 0, s>>>(sl, un, w.j, jstride, MtPlan{0u, 0xffffffffu, nullptr, nullptr});
     }
-    if (diag & 2) return 0;
+    LBDRN_LAUNCH_CHECK();
     if (w.pairs && steps) {   // the partitioned path: all permutations of the call per launch
         const int nwg = (int)((steps + PART_CHUNK - 1) / PART_CHUNK), npart = (int)((un + PART_SIZE - 1) >> PART_SHIFT);
         PartArrays A;

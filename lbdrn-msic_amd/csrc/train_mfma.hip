@@ -38,7 +38,6 @@
 #include <cmath>
 #include <cstdlib>
 #include <utility>
-#include <chrono>
 #include <vector>
 
 #include "common.hpp"
@@ -54,28 +53,19 @@ constexpr int TBC = 64;      // hidden width this kernel is built for
 constexpr int HP = 68;       // [sample][64] rows: 17 chunks of 16 B
 constexpr int TP = 36;       // [unit][32 samples] rows: 9 chunks of 16 B
 constexpr int OP = 20;       // [sample][16 channel slots] rows: 5 chunks
-#ifndef LBDRN_RED_SLICES
-#define LBDRN_RED_SLICES 8
-#endif
-constexpr int RED_SLICES = LBDRN_RED_SLICES;   // workgroup slices per reduce block: 8 x 32 float4 lanes = 512 B per slab and block.
+constexpr int RED_SLICES = 8;   // workgroup slices per reduce block: 8 x 32 float4 lanes = 512 B per slab and block.
                                 // A/B with the round-2 kernels (128 slabs; scripts/ab_lib.sh, ms per tile for one fit alone /
                                 // four in flight): 8 slices 136 / 76-80, 4: 144 / 76, 16: 144 / 77-78, 32: 140 / 77
-#ifndef LBDRN_RED_LANES
-#define LBDRN_RED_LANES 32
-#endif
-constexpr int RED_LANES = LBDRN_RED_LANES;   // float4 lanes per reduce block (x RED_SLICES threads)
-#ifndef LBDRN_SLAB_ROT
-#define LBDRN_SLAB_ROT 4
-#endif
+constexpr int RED_LANES = 32;   // float4 lanes per reduce block (x RED_SLICES threads)
 // Slab buffers a fit's steps rotate through.  The XCDs' L2s are kept coherent by hardware (a snoop filter at the Infinity
 // Cache): a store to a line that another XCD's L2 holds -- or held: the filter keeps the entry -- waits for a probe.  The
 // reduce / Adam launch reads every slab line into some L2, and with ONE buffer the next training launch's write-through
 // stores then paid for it: 5.7 us of a lone k_train_split step (profiles/r05_slab_store_ab.txt: 22.4 us a step; 15.2 with
 // the reduce launch reading nothing, 16.6 with the training launch storing nothing).  With four buffers a line is
 // rewritten three steps after it was read and the stores run free: 22.3 -> 17.1 us a step (two buffers: 17.7).  Reading
-// the slabs with non-temporal loads instead (LBDRN_RED_AUX=2) also frees the stores, but the reads themselves take 5.0
+// the slabs with non-temporal loads instead (cache policy 2, RED_AUX) also frees the stores, but the reads themselves take 5.0
 // instead of 3.7 us.
-constexpr int SLAB_ROT = LBDRN_SLAB_ROT;           // ... of the launch over k_train_split's slab pairs: 64 threads, 584 blocks at the headline shape
+constexpr int SLAB_ROT = 4;           // ... of the launch over k_train_split's slab pairs: 64 threads, 584 blocks at the headline shape
 constexpr int TRAIN_THREADS = 512;  // 8 waves: (neuron tile w = 0..3) x (sample tile st = 0..1)
 
 // ---- the wave-local steps (k_train_stream, k_train_wide): 64 samples per workgroup, 16 samples per compute wave
@@ -114,13 +104,8 @@ __host__ __device__ __forceinline__ int slot_of_feat(int k, const FeatMap& m)   
 // the map of a shape whose fused step skips the window centres (identity otherwise)
 static FeatMap centre_skipping_map(const lbdrn_geom& g, const lbdrn_net& net)
 {
-#ifdef LBDRN_EXP_KEEP_CENTRE   // (A/B build: the step multiplies the zeros as well)
-    constexpr bool keep_zero = true;
-#else
-    constexpr bool keep_zero = false;
-#endif
     const int side = 2 * g.D + 1;
-    if (!keep_zero && g.use_colors && g.relative && g.D > 0 && net.F == 2 * g.P + g.C * side * side)
+    if (g.use_colors && g.relative && g.D > 0 && net.F == 2 * g.P + g.C * side * side)
         return FeatMap{net.F - g.C, 2 * g.P, side * side, g.D * side + g.D};
     return FeatMap{net.F, 0, 0, 0};
 }
@@ -142,18 +127,6 @@ struct TrainPlan {
     int lds_x, lds_xt, lds_h, lds_ht, lds_z, lds_zt, lds_zo, lds_zot, lds_pix, lds_red, lds_floats;
 };
 
-// which fused step runs a shape this file supports: 2 = k_train_stream, 0 = the 8-wave tile kernel k_train_mfma (nl = 3).
-// A function of the shape only (the choice fixes the row-matrix layout that lbdrn_train_prepare builds and
-// lbdrn_train_epoch reads).  -DLBDRN_EXP_TILE_KERNEL: A/B build that runs every shape on the tile kernel.
-static int train_kernel_choice()
-{
-#ifdef LBDRN_EXP_TILE_KERNEL
-    return 0;
-#else
-    return 2;
-#endif
-}
-
 __host__ __device__ constexpr int stream_rp(int LQ);
 // the layer-0 quarter length of the one shape above 256 features that has a fused step (nl = 2; 256 < Fe <= 384): it runs
 // on k_train_split only -- neither k_train_stream's LDS map nor the tile kernel's fits it --, alone or in a group
@@ -164,12 +137,14 @@ static int stream_lds_total(int LQ, int NL);
 static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan* out)
 {
     if ((net.act != LBDRN_ACT_SINE && net.act != LBDRN_ACT_RELU) || net.bc != TBC || net.nl < 1 || net.nl > 3 || net.C > 16 || net.F < 1) return false;
-    if (net.act == LBDRN_ACT_RELU && (net.nl > 2 || train_kernel_choice() != 2)) return false;   // (ReLU: the streamed step and k_train_split; the nl = 3 tile kernel is the Sine network's)
+    if (net.act == LBDRN_ACT_RELU && net.nl > 2) return false;   // (ReLU: the streamed step and k_train_split; the nl = 3 tile kernel is the Sine network's)
     TrainPlan p;
     p.RP = (net.F + net.C + 3) / 4 * 4;
     p.LQ = 0;
     p.fm = FeatMap{net.F, 0, 0, 0};
-    int kind = net.nl <= 2 ? train_kernel_choice() : 0;
+    // which fused step runs the shape: 2 = k_train_stream, 0 = the 8-wave tile kernel k_train_mfma (nl = 3).  A function of
+    // the shape only (the choice fixes the row-matrix layout that lbdrn_train_prepare builds and lbdrn_train_epoch reads)
+    int kind = net.nl <= 2 ? 2 : 0;
     if (kind == 2) {   // the streamed step: features in 4 LQ slots, labels in a group of their own
         p.fm = centre_skipping_map(g, net);
         for (int lq : {16, 24, 32, 48, 52, 64})   // (24: the reference's 4-band shape -- F = 100, 96 features that can differ from zero)
@@ -357,11 +332,8 @@ __global__ void __launch_bounds__(256)
 // leave in row-major order as 16-byte stores (the per-element kernel above spends its time in 64-bit index divisions
 // and scattered uint16 gathers: 0.7 TB/s; this one: 1.8 ms for the 3.49 GB of a 2048^2 x 8 tile, 2.9 ms before the
 // table and the wide stores).
-#ifndef LBDRN_BR_TW
-#define LBDRN_BR_TW 32
-#endif
-constexpr int BR_TW = LBDRN_BR_TW;   // pixels per block.  A/B (round 4, alone on the device): 32: 1.80 ms, 64: 1.61, 128: 1.66 -- but at 64 the
-                                     // launch needs 16 KB of LDS and no longer fits beside the training workgroups of other fits (13.5 KB free)
+constexpr int BR_TW = 32;   // pixels per block.  A/B (round 4, alone on the device): 32: 1.80 ms, 64: 1.61, 128: 1.66 -- but at 64 the
+                            // launch needs 16 KB of LDS and no longer fits beside the training workgroups of other fits (13.5 KB free)
 __global__ void __launch_bounds__(256)
     k_build_rows_tiled(lbdrn_geom g, int F, int RP, int LQs, FeatMap fm, const uint16_t* __restrict__ msb,
                        const uint16_t* __restrict__ img, float* __restrict__ rows)
@@ -555,9 +527,7 @@ __global__ void __launch_bounds__(256)
 // (torch/optim/adam.py single-tensor path: lerp_, mul_/addcmul_, addcdiv_); refresh the fragment copy.
 // Block = RED_LANES float4 lanes (4*RED_LANES slab elements) x RED_SLICES workgroup slices; the final sum over
 // slices and the update are spread over 4*RED_LANES threads, one slab element each.
-#ifndef LBDRN_RED_AUX
-#define LBDRN_RED_AUX 0x00   // cache policy of k_reduce_adam's slab loads (gfx950: bit 0 sc0, bit 1 nt, bit 4 sc1)
-#endif
+constexpr int RED_AUX = 0x00;   // cache policy of k_reduce_adam's slab loads (gfx950: bit 0 sc0, bit 1 nt, bit 4 sc1)
 #ifdef LBDRN_TIMELINE
 // plain stores to distinct addresses (no atomics: they would serialise and distort what is measured)
 constexpr int TL_SLOTS = 2048;   // per step: [0] train start (workgroup 0), [1] reduce start (block 0), [2 .. 2+512) train wave ends, [514 ..) reduce block ends
@@ -620,19 +590,16 @@ __global__ void __launch_bounds__(RED_SLICES * RED_LANES)
     const int per = (nwg + RED_SLICES - 1) / RED_SLICES;
     const int w0 = slice * per, w1 = min(nwg, w0 + per);
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    // (buffer loads: the cache policy of the slab reads is an A/B switch, LBDRN_RED_AUX -- see SLAB_ROT)
+    // (buffer loads: the cache policy of the slab reads is RED_AUX -- see SLAB_ROT)
     const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(slabs), (short)0,
                                                                          (int)((size_t)nwg * (pairs ? 2 : 1) * slab_floats * 4), 0x00020000);
     const int voff = (base + 4 * l16) * 4;
     auto slab4 = [&](int slab) -> float4 {
         typedef int v4i __attribute__((ext_vector_type(4)));
-        const v4i x = __builtin_amdgcn_raw_buffer_load_b128(srs, voff + slab * slab_floats * 4, 0, LBDRN_RED_AUX);   // (the slab index differs within a wave: vector offset)
+        const v4i x = __builtin_amdgcn_raw_buffer_load_b128(srs, voff + slab * slab_floats * 4, 0, RED_AUX);   // (the slab index differs within a wave: vector offset)
         return make_float4(__int_as_float(x[0]), __int_as_float(x[1]), __int_as_float(x[2]), __int_as_float(x[3]));
     };
     int w = w0;
-#ifdef LBDRN_EXP_REDUCE_NOREAD   // (timing only: the reduce launch reads no slab -- what do its reads do to the NEXT training launch's stores?)
-    w = w1;
-#endif
     if (pairs) {
         for (; w + 8 <= w1; w += 8) {  // eight groups = sixteen loads in flight; a group's two chains first, then the groups in index order
             float4 t[8], o[8];
@@ -724,6 +691,9 @@ struct TrainArgs {
     unsigned long long* stamps;  // diagnostic build only (-DLBDRN_TRAIN_STAMPS): [nwg][16] s_memtime
     unsigned long long* tl;      // diagnostic build only (-DLBDRN_TIMELINE): [steps][4] first start / last end of the step's two launches, 100 MHz
 };
+// touch_row_bytes of a fit that steps alone (a multiple of 4, at most a row's bytes; performance only, the numbers do not
+// depend on it -- see k_train_stream's loader wave)
+constexpr int TOUCH_ROW_BYTES = 256;
 
 
 #ifdef LBDRN_TRAIN_STAMPS
@@ -757,12 +727,8 @@ struct WtBuf {  // buffer descriptor of a wave-uniform region + 16-byte write-th
     }
     __device__ __forceinline__ void store(int float_off, float a, float b, float c, float d) const
     {
-#ifdef LBDRN_PLAIN_SLAB_STORES
-        *reinterpret_cast<float4*>(base + float_off) = make_float4(a, b, c, d);
-#else
         v4i32 v = {__float_as_int(a), __float_as_int(b), __float_as_int(c), __float_as_int(d)};
         __builtin_amdgcn_raw_buffer_store_b128(v, r, float_off * 4, 0, 16 /* sc1 */);
-#endif
     }
 };
 
@@ -1135,7 +1101,6 @@ __global__ void __launch_bounds__(TRAIN_THREADS, 2) k_train_mfma(TrainArgs A)
 // sigmoid, sin and cos of the training step: a tolerance contract (1e-5 relative on the loss), so the hardware's
 // transcendentals behind a compensated reduction (lbdrn_math.hpp: fast_sigmoid, fast_sincos; 4.5e-7 absolute against 1e-7
 // for the canonical polynomials, 7 instructions against 31); the decode kernels keep the canonical arithmetic.
-// -DLBDRN_TRAIN_CANON_SINCOS puts the canonical pair back (A/B).
 __device__ __forceinline__ float train_sigmoid(float z) { return fast_sigmoid(z); }
 // The hidden activation of the fused steps and its derivative, as a template parameter of k_train_stream / k_train_split:
 // ACT = LBDRN_ACT_SINE: h = sin(30 z), dh/dz = 30 cos(30 z) (d holds the cosine);  LBDRN_ACT_RELU (torch.nn.ReLU, the
@@ -1147,11 +1112,7 @@ template <int ACT> __device__ __forceinline__ float train_act_back(float dh, flo
     if constexpr (ACT == LBDRN_ACT_RELU) return d != 0.0f ? dh : 0.0f;
     else return (dh * d) * 30.0f;
 }
-#ifdef LBDRN_TRAIN_CANON_SINCOS
-__device__ __forceinline__ void train_sincos(float x, float& sn, float& cs) { canon_sincos(x, sn, cs); }
-#else
 __device__ __forceinline__ void train_sincos(float x, float& sn, float& cs) { fast_sincos(x, sn, cs); }
-#endif
 template <int ACT> __device__ __forceinline__ void train_act(float z, float& h, float& d)
 {
     if constexpr (ACT == LBDRN_ACT_RELU) { h = z > 0.0f ? z : 0.0f; d = z > 0.0f ? 1.0f : 0.0f; }
@@ -1257,7 +1218,7 @@ static int dispatch_nl(const TrainArgs& A, int nwg, hipStream_t s)
 template <int LQ, int NL, int NT0C, int ACT>
 static int launch_stream_act(const TrainArgs& A, int nwg, int count, hipStream_t s)
 {
-    auto kern = k_train_stream<LQ, NL, LBDRN_STREAM_PD, NT0C, ACT>;
+    auto kern = k_train_stream<LQ, NL, STREAM_PD, NT0C, ACT>;
     static std::atomic<unsigned long long> configured{0};
     if (int rc = configure_lds_once(kern, A.p.wave_lds_floats * 4, configured)) return rc;
     kern<<<dim3((unsigned)nwg, (unsigned)count), STREAM_THREADS, (size_t)A.p.wave_lds_floats * 4, s>>>(A);
@@ -1276,27 +1237,21 @@ static int dispatch_stream(const TrainArgs& A, int nwg, int count, hipStream_t s
 {
     const bool one = A.net.nl == 1;
     // the shapes BASELINE.json names (F = 200: 12 strips of features that can differ from zero, F = 250: 16) and the
-    // reference's 4-band shape (F = 100: 6) run the straight-line weight-gradient schedule (-DLBDRN_EXP_STREAM_LOOP: A/B
-    // build that keeps them on the loop)
-#ifdef LBDRN_EXP_STREAM_LOOP
-    constexpr bool loop_only = true;
-#else
-    constexpr bool loop_only = false;
-#endif
+    // reference's 4-band shape (F = 100: 6) run the straight-line weight-gradient schedule
     switch (A.p.LQ) {
         case 16: return one ? launch_stream<16, 1, 0>(A, nwg, count, s) : launch_stream<16, 2, 0>(A, nwg, count, s);
         case 24:
-            if (!one && A.p.NT0 == 6 && !loop_only) return launch_stream<24, 2, 6>(A, nwg, count, s);
+            if (!one && A.p.NT0 == 6) return launch_stream<24, 2, 6>(A, nwg, count, s);
             return one ? launch_stream<24, 1, 0>(A, nwg, count, s) : launch_stream<24, 2, 0>(A, nwg, count, s);
         case 32: return one ? launch_stream<32, 1, 0>(A, nwg, count, s) : launch_stream<32, 2, 0>(A, nwg, count, s);
         case 48:
-            if (!one && A.p.NT0 == 12 && !loop_only) return launch_stream<48, 2, 12>(A, nwg, count, s);
+            if (!one && A.p.NT0 == 12) return launch_stream<48, 2, 12>(A, nwg, count, s);
             return one ? launch_stream<48, 1, 0>(A, nwg, count, s) : launch_stream<48, 2, 0>(A, nwg, count, s);
         case 52:
-            if (!one && A.p.NT0 == 13 && !loop_only) return launch_stream<52, 2, 13>(A, nwg, count, s);
+            if (!one && A.p.NT0 == 13) return launch_stream<52, 2, 13>(A, nwg, count, s);
             return one ? launch_stream<52, 1, 0>(A, nwg, count, s) : launch_stream<52, 2, 0>(A, nwg, count, s);
         default:
-            if (!one && A.p.NT0 == 16 && !loop_only) return launch_stream<64, 2, 16>(A, nwg, count, s);
+            if (!one && A.p.NT0 == 16) return launch_stream<64, 2, 16>(A, nwg, count, s);
             return one ? launch_stream<64, 1, 0>(A, nwg, count, s) : launch_stream<64, 2, 0>(A, nwg, count, s);
     }
 }
@@ -1381,9 +1336,6 @@ int mfma_train_prepare(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t
     const size_t ncol = (size_t)std::max(net.F - 2 * g.P, 0);
     const size_t tile_lds = ((size_t)g.C * side * (BR_TW + 2 * g.D) + 2 * ncol + 2 * (size_t)p.RP + (size_t)g.C * BR_TW) * 4;   // window + offsets + position table + labels
     const int64_t nblk = (int64_t)g.H * ((g.W + BR_TW - 1) / BR_TW);
-#ifdef LBDRN_EXP_PREPARE_DIAG   // (timing-only build, never the shipped library: no row matrix is built, the fit trains on whatever the buffer holds)
-    return 0;
-#endif
     if (tile_lds <= 48 * 1024 && g.D < g.H && g.D < g.W && nblk < ((int64_t)1 << 31)) {
         k_build_rows_tiled<<<(unsigned)nblk, 256, tile_lds, s>>>(g, net.F, p.RP, LQs, p.fm, msb, img, rows);
     } else {
@@ -1460,43 +1412,14 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
         LBDRN_HIP_TRY(hipMemset(tl_buf, 0, (size_t)tl_steps * TL_SLOTS * sizeof(unsigned long long)));
     }
 #endif
-#ifndef LBDRN_TOUCH_ROW_BYTES
-#define LBDRN_TOUCH_ROW_BYTES 256   // (A/B builds: 0 .. the row's bytes, a multiple of 4; performance only, the numbers do not depend on it)
-#endif
-    constexpr int touch_alone = LBDRN_TOUCH_ROW_BYTES;
     const int rows_per_wg = A.p.wave ? WB : TB;
     // A fit that has the device to itself (LBDRN_TRAIN_ALONE) steps on k_train_split where the shape has it: 256 workgroups
     // of 32 rows, every CU, two slabs per 64-row group.  The numbers are k_train_stream's bit for bit (train_split.inc).
-#ifdef LBDRN_EXP_NO_SPLIT   // (A/B build: the lone fit stays on k_train_stream)
-    const bool split = split_only(A.p);
-#else
-#ifdef LBDRN_EXP_SPLIT_ALIAS_LDS   // (timing only: every launch on k_train_split, groups included -- two workgroups per CU)
-    const bool split = split_available(A.p, net);
-#else
     const bool split = (alone && count == 1 && split_available(A.p, net)) || split_only(A.p);
-#endif
-#endif
     const int red_blocks = A.p.slab_floats / (4 * RED_LANES);
     int64_t step = step0;
     int si = 0;
-    // diagnostic (-DLBDRN_HOST_TRACE build): how long the host spends in each iteration of the launch loop
-#ifdef LBDRN_HOST_TRACE
-    constexpr bool host_trace = true;
-#else
-    constexpr bool host_trace = false;
-#endif
-    std::vector<std::pair<int, double>> slow;
-    double host_total = 0.0;
-    auto tprev = std::chrono::steady_clock::now();
-    const auto tbegin = tprev;
     for (int64_t first = 0; first < n; first += bs, ++si) {
-        if (host_trace) {
-            const auto tn = std::chrono::steady_clock::now();
-            const double us = std::chrono::duration<double, std::micro>(tn - tprev).count();
-            host_total += us;
-            if (us > 40.0) slow.emplace_back(si, us);
-            tprev = tn;
-        }
         const int B = (int)std::min<int64_t>(bs, n - first);
         const int nwg = (B + rows_per_wg - 1) / rows_per_wg;
         for (int f = 0; f < MAX_GROUP; ++f) {
@@ -1520,7 +1443,7 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
         if (A.p.wave) A.stage_in = nullptr, A.stage_out = nullptr;   // the wave-local kernels gather for themselves
         A.perm_next = perm[0] + first + bs;
         A.next_n = (int)nextB;
-        A.touch_row_bytes = (alone && count == 1) ? touch_alone : 0;   // (LBDRN_TRAIN_ALONE; see k_train_stream's loader wave)
+        A.touch_row_bytes = (alone && count == 1) ? TOUCH_ROW_BYTES : 0;   // (LBDRN_TRAIN_ALONE; see k_train_stream's loader wave)
         // (split: nwg counts the 64-row GROUPS -- the unit k_reduce_adam adds in its fixed order --, two workgroups each)
         const bool split_now = split && (B >= 2 || split_only(A.p));   // (k_train_split fetches the pixel indices two at a time: a minibatch of ONE
                                                   // row -- the tail of an epoch of n = 1 (mod batch size) rows -- steps on k_train_stream; the same bits.
@@ -1560,12 +1483,6 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
                 cnt, tr * u, g1 * u, rd * u, g2 * u, (tr + g1 + rd + g2) * u);
     }
 #endif
-    if (host_trace) {
-        fprintf(stderr, "[lbdrn host trace] %d iterations in %.0f us (%.2f us each); slower than 40 us:", si,
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tbegin).count(), host_total / std::max(si, 1));
-        for (auto& e : slow) fprintf(stderr, " %d:%.0f", e.first, e.second);
-        fprintf(stderr, "\n");
-    }
 #ifdef LBDRN_TRAIN_STAMPS
     if (A.p.wave) {   // diagnostic: mean cycles per phase over the waves of the last step
         LBDRN_HIP_TRY(hipStreamSynchronize(s));

@@ -59,16 +59,9 @@ __host__ __device__ constexpr SplitLds split_lds(int LQ)
     int o = 0;
     const int over = 2 * SPB * SP_HP + SPB * SP_OP + 2 * 64 * SP_PT;   // what moves in over the W_0 fragments behind layer 0
     L.w0 = o; o += RG * 4 * 256 > over ? RG * 4 * 256 : over;         // (LQ < 40: the region is as large as its second life needs it)
-#ifdef LBDRN_EXP_SPLIT_ALIAS_LDS   // (timing only, results garbage: the small matrices and the rows land ON the W_0 fragments, so that the
-                                   //  workgroup takes 63 KB and TWO are resident per CU -- what would two waves per SIMD buy this step?)
-    L.sm = L.w0;
-    L.xt = (G0 + 1) * SGP + 16;
-    L.x = L.w0;
-#else
     L.sm = o; o += SP_SM * 256;
     L.xt = (G0 + 1) * SGP + 16;      // one sample tile's piece
     L.x = o; o += 2 * L.xt;
-#endif
     L.h0 = o; o += SPB * SP_HP;
     L.red = o; o += 4 + 4 * 16 + 12; // loss partials of the four row quarters | output-bias partials [row quarter][slot] | pad to 16 B
     L.idx = o; o += 4 * 256;         // per wave: the 64 pixel indices of the group (512 B; the request writes 1 KB)
@@ -79,9 +72,7 @@ __host__ __device__ constexpr SplitLds split_lds(int LQ)
     L.e = a; a += SPB * SP_HP;
     L.zo = a; a += SPB * SP_OP;
     L.zt = a; a += 2 * 64 * SP_PT;
-#ifndef LBDRN_EXP_SPLIT_ALIAS_LDS
     if (a > L.sm) L.total = -1;      // (cannot happen: see `over`)
-#endif
     return L;
 }
 
@@ -194,9 +185,6 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
     const float* fsrc = F.packed + lane * 4;
     // fragment block (tile t, group g) of W_0: 256 (t G0 + g) in the packed buffer, (g 4 + t) 256 in LDS; wave w takes tile w
     auto w0_requests = [&](int g_lo, int g_hi) {
-#if defined(LBDRN_EXP_SPLIT_ALIAS_LDS) && LBDRN_EXP_SPLIT_ALIAS_LDS == 2   // (timing only: the second resident workgroup of a CU -- the other fit's -- asks
-        if (blockIdx.y == 1) return;                                       //  for no weights: what a MERGED 64-row workgroup would ingest)
-#endif
 #pragma unroll
         for (int g = g_lo; g < g_hi; ++g)
             stream_dma(fsrc + p.pk_w0 + 256 * (wv * G0 + g), lds0 + 4u * (unsigned)(L.w0 + ((g % RG) * 4 + wv) * 256));
@@ -228,20 +216,15 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
     // layer 0 is over and go out one per MFMA group of it: pushed out here, behind 25 KB per wave of requests that are, they
     // kept the wave at its issue slot -- and away from layer 0 -- while the first half had long landed
     auto small_request = [&](int b) {
-#if defined(LBDRN_EXP_SPLIT_ALIAS_LDS) && LBDRN_EXP_SPLIT_ALIAS_LDS == 2
-        if (blockIdx.y == 1) return;
-#endif
         const int blk = 4 * b + wv;
         const int src = blk < 16 ? p.pk_wh + 256 * blk : blk < 32 ? p.pk_wht + 256 * (blk - 16) : blk < 36 ? p.pk_wl + 256 * (blk - 32) : p.pk_wlt + 256 * (blk - 36);
         stream_dma(fsrc + src, lds0 + 4u * (unsigned)(L.sm + 256 * blk));
     };
-#ifndef LBDRN_NO_INDEX_TOUCH
     // The pixel indices this workgroup will ask for first in the NEXT launch (same block index, so the same XCD): that
     // launch opens with two dependent cold trips, indices then rows, and the first one then ends in a cache (what
     // k_train_stream's loader wave does as it ends).  An ordinary load, "used" when the kernel is nearly over.
     long long touched = 0;
     if (A.next_n > 0 && wv == 0 && lane < 8) touched = F.perm[A.batch_n + min(grp * WB + 8 * lane, A.next_n - 1)];   // a 64-byte piece each
-#endif
     STAMP(1);
     // requests of this wave behind the last one of phase A: W_0 B (G0 - GA) + rows B; behind phase B: the small ones issued by then
     constexpr int ROWS_B0 = split_row_requests(GA, NGR, 0), ROWS_B1 = split_row_requests(GA, NGR, 1);
@@ -478,9 +461,6 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
         }
     };
     auto put = [&](int off, const f32x4& g) {
-#ifdef LBDRN_EXP_NOSLAB   // (timing only: the gradient tiles are computed and never leave)
-        if (A.batch_n >= 0) return;
-#endif
         slabw.store(off + lane * 4, g[0], g[1], g[2], g[3]);
     };
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -585,9 +565,7 @@ __global__ void __launch_bounds__(WAVE_THREADS, 1) k_train_split(TrainArgs A)
     }
     if (w == 3 && lane < 16)   // output slots: the four row quarters' partials (loss phase), (0 + 1) + (2 + 3)
         slab[p.sl_bias + NL * TBC_W + lane] = (red[4 + lane] + red[20 + lane]) + (red[36 + lane] + red[52 + lane]);
-#ifndef LBDRN_NO_INDEX_TOUCH
     asm volatile("" ::"v"(touched));
-#endif
     STAMP(11); STAMP(12);
 #ifdef LBDRN_TIMELINE
     if (lane == 0 && uh == 0 && blockIdx.y == 0) timeline_store(A.tl, 2 + 2 * wg + st, true);   // (one wave of each pair: 512 slots)

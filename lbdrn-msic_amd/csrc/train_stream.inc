@@ -88,20 +88,10 @@ __host__ __device__ constexpr StreamLds stream_lds(int LQ, int NL)
 // groups: for each of the four compute waves two row requests, and the eight fragment blocks); the loader has issued
 // stages 0 .. PD-1 up front (fragment blocks first: they do not wait for the pixel indices), then in iteration k the
 // stage k + PD or, past the last stage, a batch of the small-matrix blocks.
-// (-DLBDRN_EXP_HALFROWS, timing only -- the step then multiplies whatever LDS held: what would a row of 7 instead of 13
-//  64-byte pieces buy?  Feature groups 6 .. G0-1 are not requested.)
-__host__ __device__ constexpr bool stream_row_wanted(int LQ, int g)
-{
-#ifdef LBDRN_EXP_HALFROWS
-    return g < 6 || g == LQ / 4;
-#else
-    return g < LQ / 4 + 1;
-#endif
-}
 __host__ __device__ constexpr int stream_row_cnt(int LQ, int s)   // row requests of stage s, per compute wave
 {
     int c = 0;
-    for (int g = 2 * s; g < 2 * s + 2; ++g) c += (g < LQ / 4 + 1) && stream_row_wanted(LQ, g);
+    for (int g = 2 * s; g < 2 * s + 2; ++g) c += g < LQ / 4 + 1;
     return c;
 }
 __host__ __device__ constexpr int stream_frag_cnt(int LQ, int s)   // fragment groups of stage s (four blocks each)
@@ -180,12 +170,8 @@ __device__ __forceinline__ void stream_for(F&& f)
     stream_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
-#ifndef LBDRN_TAIL_PLAIN
-#define LBDRN_TAIL_PLAIN 1   // the last strips of the first layer's gradient whose tiles leave as plain stores (the rest written through)
-#endif
-#ifndef LBDRN_STREAM_PD
-#define LBDRN_STREAM_PD 3
-#endif
+constexpr int TAIL_PLAIN = 1;   // the last strips of the first layer's gradient whose tiles leave as plain stores (the rest written through)
+constexpr int STREAM_PD = 3;    // k_train_stream's prefetch depth: stages the loader wave issues up front
 
 constexpr int STREAM_THREADS = WAVE_THREADS + 64;   // four compute waves + the loader
 
@@ -280,11 +266,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
             for (int g = 2 * s; g < 2 * s + 2; ++g)
                 if (g < G0)
 #pragma unroll
-                    for (int t = 0; t < 4; ++t)
-#ifndef LBDRN_EXP_NOFRAGS
-                        stream_dma(fsrc + 256 * (t * G0 + g), lds0 + 4u * (unsigned)(L.stage + (g * 4 + t) * 256));
-#endif
-                        ;
+                    for (int t = 0; t < 4; ++t) stream_dma(fsrc + 256 * (t * G0 + g), lds0 + 4u * (unsigned)(L.stage + (g * 4 + t) * 256));
         };
         // The pixel indices are requested first -- by LDS-DMA like everything else this wave asks for: 64 indices = 512 B, lane
         // l < 32 fetches elements 2 l, 2 l + 1 of the workgroup's rows (or the minibatch's last two, past its end), lanes
@@ -311,24 +293,16 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
             const int g = min(first + lane, A.batch_n - 1), l = (g - first) >> 1;
             raw = reinterpret_cast<const int64_t*>(lds + L.idx)[2 * l + (g - max(min(first + 2 * l, A.batch_n - 2), 0))];
         }
-#ifdef LBDRN_EXP_WARMROWS   // (timing only: the same 64 rows for this workgroup in every launch -- what would rows that are always warm buy?)
-        const int pix = (int)(((int64_t)blockIdx.y * 7919 + first + lane) % A.npix) + (int)(raw & 0);
-#else
         const int pix = (int)(raw < 0 ? 0 : (raw >= A.npix ? A.npix - 1 : raw));
-#endif
         const float* rsrc[4];
 #pragma unroll
         for (int v = 0; v < 4; ++v) rsrc[v] = F.rows + (size_t)__shfl(pix, 16 * v + (lane >> 2)) * RPM + 4 * (lane & 3);
         auto issue_rows = [&](int s) {
 #pragma unroll
             for (int g = 2 * s; g < 2 * s + 2; ++g)
-                if (g < NGR && stream_row_wanted(LQ, g))
+                if (g < NGR)
 #pragma unroll
-                    for (int v = 0; v < 4; ++v)
-#ifndef LBDRN_EXP_NOROWS
-                        stream_dma(rsrc[v] + 16 * g, lds0 + 4u * (unsigned)(L.x + v * WPX + g * SGP));
-#endif
-                        ;
+                    for (int v = 0; v < 4; ++v) stream_dma(rsrc[v] + 16 * g, lds0 + 4u * (unsigned)(L.x + v * WPX + g * SGP));
         };
         stream_for<PD>([&](auto s_) { if (decltype(s_)::value < NST) issue_rows(decltype(s_)::value); });
         // W_l / W_l^T blocks (SMALL): block j of 2 NH goes where it is read from
@@ -347,13 +321,10 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
             stream_wait_vm<stream_allow(LQ, NL, PD, s)>();     // stage s has landed
             stream_barrier();
             if (s + PD < NST) { issue_rows(s + PD); issue_frags(s + PD); }
-#ifndef LBDRN_EXP_NOSMALL
             else if (SMALL) issue_small(s);
-#endif
         });
         stream_wait_vm<0>();   // the small matrices too
         stream_barrier();
-#ifndef LBDRN_NO_INDEX_TOUCH
         // This wave's work is done a quarter of the way into the kernel.  Before it goes it touches the 512 bytes it will
         // want first in the NEXT launch -- the pixel indices of the same workgroup's rows of the next minibatch (same
         // block index, so the same XCD) --: that launch opens with two dependent cold trips, indices then rows, and the
@@ -381,7 +352,6 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
                 asm volatile("" ::"v"(t));   // (the load has to be made; its value is not used)
             }
         }
-#endif
         return;                // (a wave that has ended no longer counts at the workgroup's barriers)
     }
 #ifdef LBDRN_TRAIN_STAMPS
@@ -443,16 +413,6 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
             bq[g & 1] = *reinterpret_cast<const float4*>(xbase + g * SGP);
         };
         auto mfmas = [&](int g) {
-#ifdef LBDRN_EXP_X16_TIMING   // (TIMING ONLY, results garbage: what would layer 0 take on the 16-bit matrix pipe with exact operands -- W_0 in
-                              //  three pieces x the integer features in two: six 16x16x32 MFMAs per unit tile and 32 features = three per
-                              //  tile and 16-feature group of this kernel?  The operands are whatever bits the f32 ones hold.)
-            typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-            for (int pc = 0; pc < 3; ++pc)
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, aq[g & 1][t]), __builtin_bit_cast(h8, bq[g & 1]), acc[t], 0, 0, 0);
-#else
             const float bx[4] = {bq[g & 1].x, bq[g & 1].y, bq[g & 1].z, bq[g & 1].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e)
@@ -461,7 +421,6 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
                     const float4 x = aq[g & 1][t];
                     acc[t] = MFMA16(e == 0 ? x.x : e == 1 ? x.y : e == 2 ? x.z : x.w, bx[e], acc[t]);
                 }
-#endif
         };
         int vgj = 0;
         stream_for<NST>([&](auto s_) {
@@ -661,9 +620,6 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
         for (int s = 0; s < 16; ++s) dst[s] = base[s * HP];
     };
     auto put = [&](int off, const f32x4& g, bool early) {
-#ifdef LBDRN_EXP_NOSLAB   // (timing only: the gradient tiles are computed and never leave -- what do the slab stores cost a launch?)
-        if (A.batch_n >= 0) return;
-#endif
         if (early) slabw.store(off + lane * 4, g[0], g[1], g[2], g[3]);
         else slabw.store_plain(off + lane * 4, g[0], g[1], g[2], g[3]);
     };
@@ -764,27 +720,10 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
             for (int t = 0; t < 4; ++t) gs[k & 1][t][0] = gs[k & 1][t][1] = zero4;
             constexpr int nreads = k + 2 < NIT ? 16 : 0;
             item(std::integral_constant<int, k + 2>{});
-#ifdef LBDRN_EXP_X16_TIMING   // (TIMING ONLY: a strip's 64 f32 MFMAs as 4 tiles x 2 blocks of 32 samples x (dz in three pieces x the features in
-                              //  two) = 48 MFMAs of the 16-bit pipe; operands = the bits of the f32 ones)
-            {
-                typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-#pragma unroll
-                for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                    for (int pc = 0; pc < 6; ++pc)
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) {
-                            const float4 fa = make_float4(az[t][8 * kb], az[t][8 * kb + 1], az[t][8 * kb + 2], az[t][8 * kb + 3]);
-                            const float4 fb = make_float4(bb[k][8 * kb], bb[k][8 * kb + 1], bb[k][8 * kb + 2], bb[k][8 * kb + 3]);
-                            gs[k & 1][t][kb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, fa), __builtin_bit_cast(h8, fb), gs[k & 1][t][kb], 0, 0, 0);
-                        }
-            }
-#else
 #pragma unroll
             for (int s = 0; s < 16; ++s)
 #pragma unroll
                 for (int t = 0; t < 4; ++t) gs[k & 1][t][s & 1] = MFMA16(az[t][s], bb[k][s], gs[k & 1][t][s & 1]);
-#endif
             if constexpr (k == 0) {
                 put(p.sl_hid + (2 * 4 + w) * 256, stream_join(g1[2][0], g1[2][1]), true);
                 put(p.sl_hid + (3 * 4 + w) * 256, stream_join(g1[3][0], g1[3][1]), true);
@@ -792,7 +731,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, 1) k_train_stream(TrainArgs A)
             } else {
 #pragma unroll
                 for (int t = 0; t < 4; ++t)
-                    put((t * NT0C + w + 4 * (k - 1)) * 256, stream_join(gs[(k - 1) & 1][t][0], gs[(k - 1) & 1][t][1]), k - 1 < NFS - LBDRN_TAIL_PLAIN);
+                    put((t * NT0C + w + 4 * (k - 1)) * 256, stream_join(gs[(k - 1) & 1][t][0], gs[(k - 1) & 1][t][1]), k - 1 < NFS - TAIL_PLAIN);
                 stream_deal<64, nreads, 4>();
             }
 #ifdef LBDRN_STAMP_DW

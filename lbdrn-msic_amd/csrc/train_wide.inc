@@ -203,9 +203,7 @@ struct WideArgs {
 // LDS and <= 256 registers: two workgroups fit on a CU, so with two fits in flight one workgroup's activation / prologue
 // phases run under the other's MFMAs.  (A wave on 16 samples x ALL units -- round 3's shape -- is 2,944 MFMAs behind
 // 35 k cycles of phases without a single MFMA, one wave per SIMD at 412 registers, and holds half of the chip for 62 us.)
-#ifndef LBDRN_HALF_NP
-#define LBDRN_HALF_NP 2  // unit tiles per pass of a product (A/B: 8 = one pass, everything behind a product exposed)
-#endif
+constexpr int HALF_NP = 2;  // unit tiles per pass of a product (A/B: 8 = one pass, everything behind a product exposed)
 
 // sched_group_barrier recipe of one iteration of a k_train_half product: M MFMAs; ND LDS reads (the next iteration's B
 // operand / a row of X) and NV fragment requests (for a later iteration) go out one behind each of the first MFMAs; with
@@ -290,11 +288,7 @@ __global__ void __launch_bounds__(WAVE_THREADS, 2) k_train_half(WideArgs A)
 #pragma unroll
         for (int k = 0; k < NLD; ++k) {
             const float* src = A.rows + (size_t)__shfl(pix_mine, min(row, 15)) * p.RP + 4 * col;
-#ifndef LBDRN_EXP_HALF_NOROWS   // (timing only: no row is fetched, layer 0 multiplies whatever LDS holds -- what would rows that cost nothing buy?)
             if ((k & 1) == uh && lane + 64 * k < nchunk)
-#else
-            if (A.batch_n < 0)
-#endif
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                                  (__attribute__((address_space(3))) void*)(dst + k * 256), 16, 0, 0);
             row += p.w_dp; col += p.w_df;
@@ -318,12 +312,8 @@ __global__ void __launch_bounds__(WAVE_THREADS, 2) k_train_half(WideArgs A)
     // MFMAs of pass p + 1, one sin/cos pair per iteration, and only the last pass's are left over.  A pass re-reads the B
     // operand (registers / 16 LDS reads) and fetches its own NP fragment blocks per iteration: the same bytes as before,
     // in a ring of RING iterations (the request of iteration it + DIST goes out in iteration it: ~1.5 k cycles ahead).
-    constexpr int NP = NH % LBDRN_HALF_NP == 0 ? LBDRN_HALF_NP : NH, NPASS = NH / NP;
-#ifdef LBDRN_HALF_DIST
-    constexpr int DIST = LBDRN_HALF_DIST, RING = DIST + 1;   // (A/B)
-#else
+    constexpr int NP = NH % HALF_NP == 0 ? HALF_NP : NH, NPASS = NH / NP;
     constexpr int DIST = NP >= 8 ? 2 : NP >= 4 ? 4 : 6, RING = DIST + 1;   // (NP = 2: 6 against 8 / 12 iterations ahead: 332.4 / 334.1 / 336.7 ms per tile)
-#endif
     constexpr int IT0 = NPASS * G0, IT1 = NPASS * NT;
     static_assert(DIST * NP < 48, "requests in flight behind the rows: vmcnt is a 6-bit counter");
     float4 wq[RING][NP];
@@ -706,13 +696,7 @@ __device__ __forceinline__ void dw_task(const float* Aarr, int pitchA, int a_col
             for (int u = 0; u < MU; ++u) {
                 const float av = AV ? f4e(aa[s], u) : aa[s].x;
 #pragma unroll
-                for (int v = 0; v < MI; ++v) {
-#ifndef LBDRN_DW_NOMFMA
-                    acc[u][v] = MFMA16(av, f4e(bb[s][v >> 2], v & 3), acc[u][v]);
-#else               // (A/B build: the loads alone)
-                    bsum[u] += f4e(bb[s][v >> 2], v & 3);
-#endif
-                }
+                for (int v = 0; v < MI; ++v) acc[u][v] = MFMA16(av, f4e(bb[s][v >> 2], v & 3), acc[u][v]);
                 bsum[u] += av;
             }
         }
@@ -730,19 +714,12 @@ __device__ __forceinline__ void dw_task(const float* Aarr, int pitchA, int a_col
     const int niter = nsteps / SB;   // a multiple of NB: a wave's range is a multiple of 64 samples = 16 steps (or empty), NB SB divides 16
     static_assert(16 % (NB * SB) == 0, "buffer rotation");
     if (niter > 0) {
-#ifdef LBDRN_DW_NOLOAD   // (A/B build: the MFMAs alone, on whatever the first loads brought)
-#pragma unroll
-        for (int k = 0; k < NB; ++k) ld(a[k], b[k], k);
-#else
 #pragma unroll
         for (int k = 0; k < NB - 1; ++k) ld(a[k], b[k], k);
-#endif
         for (int it = 0; it < niter; it += NB) {
 #pragma unroll
             for (int k = 0; k < NB; ++k) {
-#ifndef LBDRN_DW_NOLOAD
                 ld(a[(k + NB - 1) % NB], b[(k + NB - 1) % NB], min(it + k + NB - 1, niter - 1));   // (no branch: the last trips re-read the last rows)
-#endif
                 mm(a[k], b[k]);
                 deal();
             }
@@ -798,13 +775,10 @@ __device__ __forceinline__ void dw_task(const float* Aarr, int pitchA, int a_col
 }
 
 constexpr int DW_LDS_FLOATS = 4 * 16 * DW_TS + 4 * 64;   // four waves x 16 tiles + the bias partials
-#ifndef LBDRN_DW_SB
-#define LBDRN_DW_SB 4
-#endif
-constexpr int DW_SB = LBDRN_DW_SB;   // MFMA steps per register buffer of the 64 x 64 blocks (four buffers).  -DLBDRN_DW_SB=2: 212
-                                     // registers instead of 284, two workgroups of this launch fit on a CU -- measured, same box,
-                                     // interleaved: 22.8 against 22.6 us alone, 337.3 against 338.5 ms per tile with three fits in
-                                     // flight: no difference, the deeper ring stays
+constexpr int DW_SB = 4;   // MFMA steps per register buffer of the 64 x 64 blocks (four buffers).  At 2: 212 registers
+                           // instead of 284, two workgroups of this launch fit on a CU -- measured, same box, interleaved:
+                           // 22.8 against 22.6 us alone, 337.3 against 338.5 ms per tile with three fits in flight: no
+                           // difference, the deeper ring stays
 
 template <int NT, int NL>
 __global__ void __launch_bounds__(WAVE_THREADS, 1) k_dw_wide(DwArgs A)

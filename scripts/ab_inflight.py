@@ -1,5 +1,5 @@
 """A/B aid: wall time per tile of codec.fit_many over 6 tiles with 1 and 2 fits in flight, for the train
-library named by LBDRN_HIP_LIB (e.g. a variant built with csrc/build.py --variant tile -DLBDRN_EXP_TILE_KERNEL: every shape on k_train_mfma)."""
+library named by LBDRN_HIP_LIB (e.g. a variant built with csrc/build.py --variant tl -DLBDRN_TIMELINE against the shipped one)."""
 import os, sys, time
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # like bench.py: one hardware queue per fit in flight
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

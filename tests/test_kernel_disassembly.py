@@ -67,7 +67,7 @@ def test_loader_waits_for_its_indices_behind_a_counted_wait(tmp_path):
 def test_shipped_library_exports_the_c_abi_only_and_no_kernel_uses_scratch():
     """the library is a product -- `nm -D` shows the functions of include/lbdrn_hip.h and no C++ symbol
     (-fvisibility=hidden + csrc/exports.map), no kernel in it spills (k_apply_mfma<4, 2> did: 88 registers), and its
-    sources read no environment variable (every A/B and timing-only switch is a -D of csrc/build.py --variant)."""
+    sources read no environment variable (every build switch is a -D of csrc/build.py --variant)."""
     import sys
     so = os.path.join(ROOT, "lbdrn-msic_amd", "liblbdrn_hip.so")
     if not (os.path.exists(OBJDUMP) and os.path.exists(so)):
@@ -108,3 +108,22 @@ def test_nothing_of_the_dropped_overlap_experiment_ships():
         #  agent scope between two launches)
         for m in re.finditer(r"__builtin_amdgcn_fence\(([^)]*)\)", src):
             assert '"agent"' not in m.group(1) and '"system"' not in m.group(1) and m.group(1).strip().endswith('"wavefront"'), f"{f}: {m.group(0)}"
+
+
+def test_the_only_build_switches_are_the_measurement_instruments():
+    """The A/B alternatives, timing-only arms and fixed numeric tunables of rounds 1-6 were removed from csrc/ (DESIGN 1,
+    "Build switches"; they last exist in commit ac69733).  What is left to switch at build time are the four instruments:
+    the in-kernel phase stamps and the per-step timeline.  Every LBDRN_ macro an #if / #ifdef / #ifndef / #elif line of the
+    sources tests, inside defined(...) too, is one of them: a new measurement switch is added to this list on purpose."""
+    instruments = {"LBDRN_TRAIN_STAMPS", "LBDRN_APPLY_STAMPS", "LBDRN_STAMP_DW", "LBDRN_TIMELINE"}
+    csrc = os.path.join(ROOT, "lbdrn-msic_amd", "csrc")
+    seen = set()
+    for f in sorted(os.listdir(csrc)):
+        if not f.endswith((".hip", ".inc", ".hpp")):
+            continue
+        src = open(os.path.join(csrc, f)).read().replace("\\\n", " ")   # (continued directive lines as one)
+        for m in re.finditer(r"^[ \t]*#[ \t]*(?:if|ifdef|ifndef|elif|elifdef|elifndef)\b(.*)$", src, re.M):
+            names = set(re.findall(r"\bLBDRN_[A-Z0-9_]+", m.group(1).split("//")[0]))
+            assert names <= instruments, f"{f}: {m.group(0).strip()[:80]} tests {sorted(names - instruments)}"
+            seen |= names
+    assert seen == instruments, sorted(instruments - seen)
