@@ -278,6 +278,26 @@ int lbdrn_plane_encode(const uint16_t *planes, int32_t C, int32_t H, int32_t W, 
 int lbdrn_plane_decode(const void *body, size_t body_bytes, int32_t C, int32_t H, int32_t W, uint16_t *planes,
                        int32_t *status, void *workspace, size_t workspace_bytes, void *stream);
 
+/* MSB-plane payload "jp2-gpu" -- the reference's own payload format: a complete lossless JPEG 2000 file (.jp2) with the
+ * coding parameters `gdal_translate -of JP2OpenJPEG -co QUALITY=100 -co REVERSIBLE=YES` asks for (encode.py:137) --
+ * unsigned components of `bits` (8 or 16) bits, 1024 x 1024 tiles when H or W exceeds 1024, LRCP, one layer, 64 x 64 code
+ * blocks of style 0, reversible 5/3 wavelet with up to five decompositions, no quantisation -- written from planes
+ * [C][H][W] uint16 in HBM.  The wavelet and the block coder (T.800 Annexes C, D, F) run on the device (csrc/jp2k.hip), the
+ * packet headers and the boxes on the host; any JPEG 2000 decoder reads the result (this package: lbdrn_jp2_decode).
+ * There is no decoder here.  1 <= C <= 16384, 1 <= H, W <= 32768.
+ *   lbdrn_jp2k_block_count  code blocks of the geometry (host only, no device needed); 0 for a bad geometry
+ *   lbdrn_jp2k_bound        output bytes that always suffice (the coder's expansion on incompressible planes included)
+ *   lbdrn_jp2k_workspace    device scratch bytes
+ *   lbdrn_jp2k_encode       writes the file to out (HOST memory, like the weight payload's calls) and its length to
+ *                           *nbytes; synchronises `stream`.  LBDRN_E_ARG for a bad argument or a value that does not
+ *                           fit `bits`, LBDRN_E_WORKSPACE when the workspace or `capacity` is too small (the needed
+ *                           size is in the message); nothing is written beyond `capacity`. */
+int64_t lbdrn_jp2k_block_count(int32_t C, int32_t H, int32_t W);
+size_t lbdrn_jp2k_bound(int32_t C, int32_t H, int32_t W);
+size_t lbdrn_jp2k_workspace(int32_t C, int32_t H, int32_t W);
+int lbdrn_jp2k_encode(const uint16_t *planes, int32_t C, int32_t H, int32_t W, int32_t bits, void *out, size_t capacity,
+                      size_t *nbytes, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Weight payload -- stands where the reference calls fpzip (encode.py:129 `fpzip.compress(params,
  * precision=args.precision, order='C')`, decode.py:113 `fpzip.decompress(...)[0][0][0]`): the float32 parameter
  * vector (state_dict order, a10) as a 1-D fpzip stream at `precision` bits (2..32; 0 = 32).  The lossy value map is

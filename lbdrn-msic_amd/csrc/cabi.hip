@@ -27,6 +27,11 @@ int plane_decode(const void* body, size_t body_bytes, int C, int H, int W, uint1
 int64_t mt19937_jump_poly(int segment, uint32_t* out);
 int randperm_batch(const uint64_t* seeds, int count, int64_t n, int64_t* out, void* ws, size_t ws_bytes,
                    hipStream_t s);
+int64_t jp2k_block_count(int C, int H, int W);
+size_t jp2k_bound(int C, int H, int W);
+size_t jp2k_workspace(int C, int H, int W);
+int jp2k_encode(const uint16_t* planes, int C, int H, int W, int bits, uint8_t* out, size_t cap, size_t* nbytes, void* ws,
+                size_t ws_bytes, hipStream_t s);
 size_t weights_bound(int64_t n);
 int weights_encode(const float* values, int64_t n, int precision, uint8_t* out, size_t cap, size_t* nbytes);
 int weights_info(const uint8_t* in, size_t nbytes, int64_t* n, int* precision);
@@ -379,6 +384,17 @@ int lbdrn_plane_decode(const void* body, size_t body_bytes, int32_t C, int32_t H
     LBDRN_REQUIRE(C >= 1 && H >= 1 && W >= 1 && C <= 65535, "bad raster geometry");
     NEED_DEVICE();
     return plane_decode(body, body_bytes, C, H, W, planes, status, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int64_t lbdrn_jp2k_block_count(int32_t C, int32_t H, int32_t W) { return jp2k_block_count(C, H, W); }
+size_t lbdrn_jp2k_bound(int32_t C, int32_t H, int32_t W) { return jp2k_bound(C, H, W); }
+size_t lbdrn_jp2k_workspace(int32_t C, int32_t H, int32_t W) { return jp2k_workspace(C, H, W); }
+
+int lbdrn_jp2k_encode(const uint16_t* planes, int32_t C, int32_t H, int32_t W, int32_t bits, void* out, size_t capacity,
+                      size_t* nbytes, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (int rc = device_ok()) return rc;
+    return jp2k_encode(planes, C, H, W, bits, (uint8_t*)out, capacity, nbytes, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t lbdrn_weights_bound(int64_t n) { return n < 0 ? 0 : weights_bound(n); }

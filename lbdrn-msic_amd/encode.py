@@ -24,7 +24,8 @@ from lbdrn_hip.features import FeatCfg
 from LBDRNdataset import tile_windows
 
 DEVICE = "cuda:0"
-BASE_CODEC = os.environ.get("LBDRN_BASE_CODEC", "LBB2")   # "jp2": JPEG 2000 through OpenJPEG, what the reference writes
+BASE_CODEC = os.environ.get("LBDRN_BASE_CODEC", "LBB2")   # "jp2": JPEG 2000 through OpenJPEG, what the reference writes;
+                                                          # "jp2-gpu": the same format coded on the GPU (csrc/jp2k.hip)
                                                           # (encode.py:137); "LBB1": the portable host payload of older files
 REPORT_BOTH = os.environ.get("LBDRN_REPORT_BOTH_BPSP", "") not in ("", "0")   # also log the size of the payload format NOT
 # written (JPEG 2000 costs 2-3 s of one host core per 8 x 2048^2 tile: off by default)
@@ -105,8 +106,8 @@ def report_and_pack(args, res, base_ahead=None):
         t0 = time.time()
         base_payload = base_ahead()
         logger.log.info(f"MSB payload ({BASE_CODEC}) coded beside the fit; waited {time.time() - t0:.3f}s more for it")
-    elif BASE_CODEC == "LBB2":
-        base_payload = container.encode_base(res.msb_device, device=DEVICE, as_uint8=res.msb_max <= 255)
+    elif BASE_CODEC == "LBB2" or BASE_CODEC.lower() == container.JP2_GPU_CODEC:   # coded from the plane in HBM
+        base_payload = container.encode_base(res.msb_device, codec=BASE_CODEC, device=DEVICE, as_uint8=res.msb_max <= 255)
     else:
         base_payload = container.encode_base(_host_msb(res), codec=BASE_CODEC)
     logger.log.info(f"MSB: {len(base_payload)} bytes: bpsp={len(base_payload) * 8 / res.n_subpixels}")
@@ -171,6 +172,10 @@ def main(argv=None, shard_tiles=None):
             container.check_weight_precision(args.precision)
         except ValueError as e:
             parser.error(str(e))
+    try:   # likewise an MSB payload codec nobody knows (LBDRN_BASE_CODEC)
+        container.check_base_codec(BASE_CODEC)
+    except ValueError as e:
+        parser.error(str(e))
     rank, world = 0, 1
     if shard_tiles is None:
         shard_tiles = shard.env_world()[1] > 1

@@ -250,6 +250,17 @@ def decode_weights(buf, expected=None):
 
 # ---------------------------------------------------------------- MSB-plane payload
 
+JP2_HOST_CODECS = ("jp2", "jpeg2000", "jp2openjpeg")   # JPEG 2000 through OpenJPEG on the host (lbdrn_hip/jp2.py)
+JP2_GPU_CODEC = "jp2-gpu"                               # the same format, coded on the GPU (csrc/jp2k.hip)
+
+
+def check_base_codec(codec):
+    """The MSB payload codec names encode_base takes; anything else is refused (ValueError) before any work is done."""
+    if codec.lower() in JP2_HOST_CODECS or codec.lower() == JP2_GPU_CODEC or codec in ("LBB2", "LBB1"):
+        return codec
+    raise ValueError(f"unknown MSB payload codec {codec!r}")
+
+
 def encode_base(msb, codec="LBB2", device="cuda:0", as_uint8=None):
     """Lossless MSB plane [C,H,W] (uint8 when max <= 255 else uint16, ref LBDRNdataset.py:100); stands where
     the reference runs gdal_translate to JPEG 2000 (ref encode.py:137).
@@ -257,8 +268,19 @@ def encode_base(msb, codec="LBB2", device="cuda:0", as_uint8=None):
     LBB2 (default): coded on the GPU by lbdrn_plane_encode (csrc/plane_codec.hip) -- msb may be a numpy array
     or the device tensor the fit left in HBM (then as_uint8 says which dtype the decoder hands back).  LBB1: the portable host codec of earlier bitstreams (plane
     predictor + LZMA; a minute per 8 x 2048^2 tile), kept so that those files still decode and for hosts
-    that only need to write small rasters."""
-    if codec.lower() in ("jp2", "jpeg2000", "jp2openjpeg"):   # ref encode.py:137
+    that only need to write small rasters.  jp2: a lossless JPEG 2000 file through OpenJPEG on the host.  jp2-gpu: the
+    same format with the same coding parameters, wavelet and block coder on the GPU (lbdrn_jp2k_encode, csrc/jp2k.hip),
+    from a numpy array or the device tensor like LBB2; decode_base reads either through OpenJPEG."""
+    check_base_codec(codec)
+    if codec.lower() == JP2_GPU_CODEC:
+        from . import ops
+        if isinstance(msb, np.ndarray):
+            bits = 8 if msb.dtype == np.uint8 else 16
+            planes = ops.to_device_u16(np.ascontiguousarray(msb).astype(np.uint16), device)
+        else:
+            planes, bits = msb, (8 if as_uint8 else 16)
+        return ops.jp2k_encode(planes, bits)
+    if codec.lower() in JP2_HOST_CODECS:   # ref encode.py:137
         from . import jp2
         if not isinstance(msb, np.ndarray):
             from . import ops

@@ -328,6 +328,26 @@ def plane_encode(planes):
     return body[:int(nbytes.item())].cpu().numpy().tobytes()
 
 
+def jp2k_encode(planes, bits, out=None):
+    """[C,H,W] uint16 planes in HBM -> a complete lossless .jp2 file as host bytes (lbdrn_jp2k_encode, csrc/jp2k.hip):
+    the wavelet and the block coder run on the device, on the current stream, which the call synchronises.  bits: 8 or
+    16, the precision the file announces (every value must fit it)."""
+    _need_cuda(planes)
+    planes = _u16(planes.contiguous())
+    C, H, W = planes.shape
+    dev = planes.device
+    cap = lib().lbdrn_jp2k_bound(C, H, W)
+    if not cap:
+        raise _lib.LbdrnError(f"lbdrn_jp2k_encode: geometry {C} x {H} x {W} is not supported")
+    if out is None:
+        out = np.empty(cap, np.uint8)   # (untouched pages cost nothing: the file is a fraction of the bound)
+    n = ctypes.c_size_t()
+    ws = torch.empty(max(lib().lbdrn_jp2k_workspace(C, H, W), 1), dtype=torch.uint8, device=dev)
+    _call(lib().lbdrn_jp2k_encode, planes, _ptr(planes), C, H, W, int(bits), out.ctypes.data_as(ctypes.c_void_p), out.size,
+                                  ctypes.byref(n), _ptr(ws), ws.numel())
+    return out[:n.value].tobytes()
+
+
 def plane_decode(body, C, H, W, device):
     """LBB2 body (bytes) -> [C,H,W] uint16 planes in HBM (int16 storage).  Raises on a malformed stream."""
     raw = torch.frombuffer(bytearray(body), dtype=torch.uint8).to(device)
