@@ -9,7 +9,8 @@
 //                   vertical before horizontal as T.800 F.4.2 orders it (integer lifting does not commute)
 //   k_jp2k_blocks   one wave per code block: the wave stages the block into LDS as sign/magnitude in stripe-column
 //                   order and finds its top bit-plane, then lane 0 runs the serial coder of jp2k_t1.inc on LDS state
-//                   (18.7 KB per block: eight blocks per CU) and writes the bytes into the block's slot
+//                   (19.4 KB per block -- mag 16384 + st 2376 + mqtab 376 + zc 256 + cx 32 + top 4 = 19428 bytes: eight
+//                   blocks per CU) and writes the bytes into the block's slot
 //   k_jp2k_compact  packs the slots back to back behind an exclusive scan of the lengths
 //
 // Every write is clamped: a block's bytes to its slot (an overflow is counted and reported, never written), the file to

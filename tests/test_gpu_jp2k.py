@@ -1,6 +1,8 @@
-"""The GPU JPEG 2000 encoder (base codec "jp2-gpu": lbdrn_jp2k_encode, csrc/jp2k.hip) judged by OpenJPEG: the files it
-writes decode to exactly the planes that went in, carry the marker segments of the host codec's files (lbdrn_hip/jp2.py,
-csrc/jp2_shim.c), and have their size up to the arithmetic coder's termination."""
+"""The GPU JPEG 2000 encoder (base codec "jp2-gpu": lbdrn_jp2k_encode, csrc/jp2k.hip) judged twice.  By the oracle
+(oracle/jp2k_oracle.c, proven on the CPU by tests/test_jp2k_oracle.py): its files equal the oracle's byte for byte, and a
+mismatch names the first differing code block and the stage at fault; these tests need no OpenJPEG.  And by OpenJPEG,
+where liblbdrn_jp2.so is built: the files decode to exactly the planes that went in, carry the marker segments of the host
+codec's files (lbdrn_hip/jp2.py, csrc/jp2_shim.c), and have their size up to the arithmetic coder's termination."""
 import ctypes
 import io
 import os
@@ -12,6 +14,10 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+
+import jp2k as oracle  # noqa: E402
+from test_jp2k_oracle import NEW_GEOMETRY_PLANES, fuzz_planes, planes_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -226,3 +232,125 @@ def test_cli_round_trip_with_the_gpu_jpeg2000_payload(dev, jp2, tmp_path):
         other = re.search(r"MSB as (jp2|LBB2): (\d+) bytes: bpsp=", logs)
         assert other and other.group(1) == ("LBB2" if codec_name == "jp2-gpu" else "jp2")
     assert np.array_equal(recs["jp2-gpu"], recs["LBB2"]) and np.array_equal(recs["jp2-gpu"] >> 5, img >> 5)
+
+
+# ------------------------------------------------------------------ the device against the oracle, byte for byte
+
+def assert_equals_oracle(x, dev, label=""):
+    """the device's file of x equals the oracle's; otherwise the message names the first differing code block, what
+    differs in it, and whether the block coder or the transform / staging is at fault.  Returns the file."""
+    g = gpu_encode(x, dev)
+    o = oracle.encode(x)
+    assert g == o, f"jp2-gpu {label} {x.shape} {x.dtype}: {oracle.first_difference(g, o, x)}"
+    return g
+
+
+@pytest.mark.parametrize("shape", SYNTH, ids=lambda s: "x".join(map(str, s)))
+def test_synthetic_planes_equal_the_oracle_byte_for_byte(shape, dev):
+    from lbdrn_hip.synth import synthetic_tile
+    assert_equals_oracle(np.ascontiguousarray(synthetic_tile(0, *shape) >> 5), dev, "synthetic")
+
+
+def test_eight_bit_empty_incompressible_and_spike_planes_equal_the_oracle(dev):
+    from lbdrn_hip.synth import synthetic_tile
+    assert_equals_oracle(np.ascontiguousarray(synthetic_tile(0, 3, 300, 517) >> 8).astype(np.uint8), dev, "8 bits")
+    assert_equals_oracle(np.zeros((2, 100, 130), np.uint16), dev, "zero")
+    assert_equals_oracle(np.full((2, 100, 130), 32768, np.uint16), dev, "zero after the level shift")
+    assert_equals_oracle(np.full((3, 1100, 90), 1234, np.uint16), dev, "constant")
+    assert_equals_oracle(np.full((1, 70, 70), 200, np.uint8), dev, "constant, 8 bits")
+    assert_equals_oracle(np.random.default_rng(7).integers(0, 65536, (2, 257, 300)).astype(np.uint16), dev, "uniform random")
+    z = np.zeros((1, 130, 140), np.uint16)
+    z[0, 77, 91] = 65535
+    assert_equals_oracle(z, dev, "spike")
+    z = np.zeros((2, 1030, 1100), np.uint16)
+    z[1, 1029, 1099] = 65535
+    assert_equals_oracle(z, dev, "spike in the last tile's corner")
+
+
+@pytest.mark.parametrize("shape", NEW_GEOMETRY_PLANES, ids=lambda s: "x".join(map(str, s)))
+def test_tile_edge_geometries_equal_the_oracle(shape, dev):
+    """sides of exactly 1024 and of 1025, one-pixel-wide last tiles, H = 1 tiled, ragged last tiles, 32768 on a side"""
+    assert_equals_oracle(planes_of("synth", shape, 16), dev, "geometry")
+    if shape[1] * shape[2] < 400000:
+        assert_equals_oracle(planes_of("uniform", shape, 8), dev, "geometry, 8 bits uniform")
+
+
+def test_period_two_patterns_keep_every_block_within_its_bands_bit_planes(dev):
+    """stripes and checkerboards of 0 / 65535 (0 / 255) maximise the high-pass magnitudes; a block with more bit-planes than
+    its band announces would get a negative zero-bit-plane count, which put_packet_header writes without complaint"""
+    F = oracle.F
+    for shape in ((1, 300, 517), (2, 1030, 90), (1, 64, 64), (1, 7, 1100)):
+        for stat in ("stripes_h", "stripes_v", "checker"):
+            for bits in (16, 8):
+                g = assert_equals_oracle(planes_of(stat, shape, bits), dev, stat)
+                rec = oracle.parse(g)
+                assert (rec[:, F["numbps"]] <= rec[:, F["mb"]]).all(), (shape, stat, bits, rec[rec[:, F["numbps"]] > rec[:, F["mb"]]][:3])
+                assert rec[:, F["numbps"]].max() >= bits, (shape, stat, bits)      # (the patterns do reach the high planes)
+
+
+def test_a_seeded_fuzz_of_shapes_depths_and_statistics_equals_the_oracle(dev):
+    n = 0
+    for shape, bits, stat, x in fuzz_planes(48, 20261016):
+        assert_equals_oracle(x, dev, f"fuzz case {n} ({stat}, {bits} bits)")
+        n += 1
+    assert n == 48
+
+
+@pytest.mark.parametrize("side", [6000, 7550])
+def test_one_component_of_a_scene_equals_the_oracle(side, dev):
+    """The two scene sizes of README.md, one component each (36 and 57 million samples in 36 and 64 tiles).  The oracle's
+    coding time decides how much of a scene is affordable: one core codes 1 x 6000 x 6000 in 7.6 s and
+    1 x 7550 x 7550 in 11.2 s (plus 4 s and 6 s to make the planes), so all eight (four) components would cost over a minute of a shared machine's
+    time per run; the geometry is the same for every component, one is coded."""
+    from lbdrn_hip.synth import synthetic_tile
+    assert_equals_oracle(np.ascontiguousarray(synthetic_tile(0, 1, side, side) >> 5), dev, "scene")
+
+
+def test_poisoned_workspace_changes_nothing_and_the_guard_behind_it_stays(dev):
+    """The caller's workspace holds whatever the last user left: the file from a workspace pre-filled with 0xA5 equals the
+    one from a zeroed workspace, and nothing is written behind lbdrn_jp2k_workspace bytes (a guard region in the same
+    tensor, memory this test owns).  16 bits, 8 bits (whose carve differs from the 16-bit sizing), and a small sparse
+    image coded straight after a large dense one in the same workspace."""
+    import torch
+    from lbdrn_hip import _lib, ops
+    L = _lib.lib()
+    GUARD = 1 << 16
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def call(planes, x, bits, ws, ws_bytes):
+        C, H, W = x.shape
+        cap = L.lbdrn_jp2k_bound(C, H, W)
+        buf = np.zeros(cap, np.uint8)
+        n = ctypes.c_size_t(0)
+        rc = L.lbdrn_jp2k_encode(ctypes.c_void_p(planes.data_ptr()), C, H, W, bits, buf.ctypes.data_as(ctypes.c_void_p), cap,
+                                 ctypes.byref(n), ctypes.c_void_p(ws.data_ptr()), ws_bytes, stream)
+        assert rc == 0, (L.lbdrn_last_error() or b"").decode()
+        torch.cuda.synchronize(dev)
+        return buf[:n.value].tobytes()
+
+    dense = np.random.default_rng(11).integers(0, 65536, (2, 1030, 300)).astype(np.uint16)
+    sparse = planes_of("sparse", (1, 70, 90), 16)
+    eight = planes_of("uniform", (3, 129, 200), 8)
+    for x in (dense, eight, planes_of("synth", (2, 300, 517), 16)):
+        bits = 8 * x.dtype.itemsize
+        planes = ops.to_device_u16(x.astype(np.uint16), dev)
+        nws = L.lbdrn_jp2k_workspace(*x.shape)
+        ws = torch.empty(nws + GUARD, dtype=torch.uint8, device=dev)
+        ws.zero_()
+        ws[nws:] = 0xA5
+        clean = call(planes, x, bits, ws, nws)
+        ws.fill_(0xA5)
+        dirty = call(planes, x, bits, ws, nws)
+        assert dirty == clean, f"{x.shape} {bits} bits: {oracle.first_difference(dirty, clean, x)}"
+        assert clean == oracle.encode(x), oracle.first_difference(clean, oracle.encode(x), x)
+        assert bool((ws[nws:] == 0xA5).all()), f"{x.shape} {bits} bits: bytes behind the workspace were written"
+    # the small sparse image straight after the large dense one, in the workspace the dense one left behind
+    nws = L.lbdrn_jp2k_workspace(*dense.shape)
+    ws = torch.empty(nws + GUARD, dtype=torch.uint8, device=dev)
+    ws.fill_(0xA5)
+    assert call(ops.to_device_u16(dense, dev), dense, 16, ws, nws) == oracle.encode(dense)
+    small = L.lbdrn_jp2k_workspace(*sparse.shape)
+    assert small < nws
+    got = call(ops.to_device_u16(sparse, dev), sparse, 16, ws, nws)
+    assert got == oracle.encode(sparse), oracle.first_difference(got, oracle.encode(sparse), sparse)
+    assert bool((ws[nws:] == 0xA5).all()), "bytes behind the workspace were written"
