@@ -83,6 +83,18 @@ static int net_matches(const lbdrn_geom* g, const lbdrn_net* net)
     return 0;
 }
 
+// The sizing functions are the contract: a workspace shorter than what lbdrn_apply_workspace / lbdrn_train_workspace
+// returned for this shape is refused here, before any launch, whichever kernels the call would go on to choose (their
+// own carve may need less than the maximum over the paths that the sizing function reports).
+static int workspace_fits(const char* what, const void* ws, size_t have, size_t need)
+{
+    if (!ws || have < need) {
+        set_error("%s workspace too small: %zu < %zu", what, have, need);
+        return LBDRN_E_WORKSPACE;
+    }
+    return 0;
+}
+
 extern "C" {
 
 const char* lbdrn_last_error(void) { return last_error(); }
@@ -209,6 +221,7 @@ int lbdrn_decode_fused(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t
     NEED_DEVICE();
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
+    if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
     if (use_mfma)
         return mfma_decode(*g, *net, msb, params, out, y_out, workspace, workspace_bytes, (hipStream_t)stream);
     return generic_decode(*g, *net, msb, params, out, y_out, workspace, workspace_bytes, (hipStream_t)stream);
@@ -228,6 +241,7 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
     path &= ~(LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16);
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
+    if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
     if (use_mfma)
         return mfma_eval_sse(*g, *net, img, msb, params, sse, workspace, workspace_bytes, background, fast, x16,
                              (hipStream_t)stream);
@@ -257,6 +271,7 @@ int lbdrn_train_prepare(const lbdrn_geom* g, const lbdrn_net* net, const uint16_
         set_error("fused MFMA train kernel does not support this shape or minibatch size");
         return LBDRN_E_UNSUPPORTED;
     }
+    if (int rc = workspace_fits("train", workspace, workspace_bytes, lbdrn_train_workspace(g, net, batch_size))) return rc;
     if (ok && path != LBDRN_PATH_GENERIC)
         return mfma_train_prepare(*g, *net, img, msb, batch_size, workspace, workspace_bytes, (hipStream_t)stream);
     return 0;
@@ -282,6 +297,7 @@ int lbdrn_train_epoch(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t*
         return LBDRN_E_UNSUPPORTED;
     }
     LBDRN_REQUIRE(path >= LBDRN_PATH_AUTO && path <= LBDRN_PATH_MFMA, "unknown path %d", path);
+    if (int rc = workspace_fits("train", workspace, workspace_bytes, lbdrn_train_workspace(g, net, batch_size))) return rc;
     if (ok && path != LBDRN_PATH_GENERIC)
         return mfma_train_epoch(*g, *net, img, msb, perm, n, batch_size, params, exp_avg, exp_avg_sq,
                                 adam_step0, lr, losses, workspace, workspace_bytes, (hipStream_t)stream, alone);
@@ -325,6 +341,8 @@ int lbdrn_train_epoch_group(int32_t count, const lbdrn_geom* const* g, const lbd
     path &= ~LBDRN_TRAIN_ALONE;
     LBDRN_REQUIRE(path >= LBDRN_PATH_AUTO && path <= LBDRN_PATH_MFMA, "unknown path %d", path);
     NEED_DEVICE();
+    for (int f = 0; f < count; ++f)
+        if (int rc = workspace_fits("train", workspace[f], workspace_bytes, lbdrn_train_workspace(g[f], net, batch_size))) return rc;
     // side by side on the fused step where the shape has one; otherwise (and for any shape the group launch does not
     // take) one after another: same numbers either way
     if (count > 1 && path != LBDRN_PATH_GENERIC && mfma_train_supported(*g[0], *net, batch_size)) {
