@@ -1,4 +1,4 @@
-"""Build liblbdrn_hip.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build liblbdrn_hip.so and liblbdrn_jp2k_dec.so for gfx950 with hipcc (in-tree, next to the Python host code).
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -44,6 +44,30 @@ def build_jp2(force=False):
     return None
 
 
+JP2K_DEC_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_jp2k_dec.so")
+JP2K_DEC_SRCS = ["jp2k_dec.hip"]
+JP2K_DEC_DEPS = ["jp2k_t1.inc", "jp2k_t2.inc", "jp2k_t1d.inc", "jp2k_t2d.inc", "common.hpp", "exports_jp2k_dec.map",
+                 "../../include/lbdrn_hip.h", "../../include/lbdrn_jp2k_dec.h"]
+
+
+def build_jp2k_dec(force=False):
+    """liblbdrn_jp2k_dec.so (include/lbdrn_jp2k_dec.h): the GPU decoder of the JPEG 2000 payload, a library of its own
+    beside liblbdrn_hip.so -- same compiler, same flags, its own object files and version script."""
+    if not force and os.path.exists(JP2K_DEC_OUT):
+        t = os.path.getmtime(JP2K_DEC_OUT)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in JP2K_DEC_SRCS + JP2K_DEC_DEPS + ["build.py"]):
+            return JP2K_DEC_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = []
+    for src in JP2K_DEC_SRCS:
+        obj = os.path.join(HERE, src.replace(".hip", ".o"))
+        objs.append(obj)
+        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
+                           "-Wl,--version-script=" + os.path.join(HERE, "exports_jp2k_dec.map"), "-o", JP2K_DEC_OUT] + objs)
+    return JP2K_DEC_OUT
+
+
 def stale():
     if not os.path.exists(OUT):
         return True
@@ -53,6 +77,8 @@ def stale():
 
 def build(force=False, extra=(), out=None):
     out = out or OUT
+    if out == OUT:
+        build_jp2k_dec(force)
     if out == OUT and not force and not stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -83,4 +109,5 @@ if __name__ == "__main__":
                     out=os.path.join(os.path.dirname(HERE), f"liblbdrn_hip_{sys.argv[k + 1]}.so")))
     else:
         print(build(force="--force" in sys.argv))
+        print(JP2K_DEC_OUT)
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

@@ -270,7 +270,8 @@ def encode_base(msb, codec="LBB2", device="cuda:0", as_uint8=None):
     predictor + LZMA; a minute per 8 x 2048^2 tile), kept so that those files still decode and for hosts
     that only need to write small rasters.  jp2: a lossless JPEG 2000 file through OpenJPEG on the host.  jp2-gpu: the
     same format with the same coding parameters, wavelet and block coder on the GPU (lbdrn_jp2k_encode, csrc/jp2k.hip),
-    from a numpy array or the device tensor like LBB2; decode_base reads either through OpenJPEG."""
+    from a numpy array or the device tensor like LBB2; decode_base reads either through OpenJPEG or the GPU decoder
+    (LBDRN_BASE_DECODER, _decode_jp2)."""
     check_base_codec(codec)
     if codec.lower() == JP2_GPU_CODEC:
         from . import ops
@@ -313,17 +314,51 @@ def encode_base(msb, codec="LBB2", device="cuda:0", as_uint8=None):
     return BASE_PRIVATE_MAGIC + struct.pack(">BHII", code, C, H, W) + body
 
 
+BASE_DECODERS = ("auto", "openjpeg", "gpu")
+
+
+def base_decoder():
+    """Who reads a JPEG 2000 MSB payload: LBDRN_BASE_DECODER = auto (default) | openjpeg | gpu."""
+    import os
+    name = (os.environ.get("LBDRN_BASE_DECODER") or "auto").lower()
+    if name not in BASE_DECODERS:
+        raise ValueError(f"LBDRN_BASE_DECODER={name!r}: one of {', '.join(BASE_DECODERS)}")
+    return name
+
+
+def _decode_jp2(buf, device, keep_on_device):
+    """auto: OpenJPEG on the host where liblbdrn_jp2.so is built (its behaviour and its errors are unchanged), the GPU
+    decoder (lbdrn_hip/jp2k_dec.py, csrc/jp2k_dec.hip) where it is not.  openjpeg: OpenJPEG only.  gpu: the GPU decoder; a
+    file it answers LBDRN_E_UNSUPPORTED for goes to OpenJPEG where that is built and raises with the library's message
+    where it is not.  The GPU decoder leaves the planes in HBM: keep_on_device returns that tensor."""
+    from . import jp2, jp2k_dec
+    name = base_decoder()
+    use_gpu = name == "gpu" or (name == "auto" and not jp2.available() and jp2k_dec.available())
+    if use_gpu:
+        try:
+            planes, bits = jp2k_dec.decode(buf, device)
+        except jp2k_dec.Jp2kDecUnsupported:
+            if name != "gpu" or not jp2.available():
+                raise
+        else:
+            if keep_on_device:
+                return planes
+            x = planes.cpu().numpy().view(np.uint16)
+            return x.astype(np.uint8) if bits <= 8 else x
+    x = jp2.decode(buf)
+    if keep_on_device:
+        from . import ops
+        return ops.to_device_u16(x.astype(np.uint16), device)
+    return x
+
+
 def decode_base(buf, device="cuda:0", keep_on_device=False):
-    """MSB payload -> [C,H,W] numpy (uint8 / uint16 as encoded).  keep_on_device: an LBB2 payload is returned
-    as the device tensor it was decoded into (uint16 bits, int16 storage) -- decode.py feeds it straight to
-    the apply kernel."""
+    """MSB payload -> [C,H,W] numpy (uint8 / uint16 as encoded).  keep_on_device: an LBB2 payload, and a JPEG 2000 payload
+    read by the GPU decoder, is returned as the device tensor it was decoded into (uint16 bits, int16 storage) --
+    decode.py feeds it straight to the apply kernel."""
     from . import jp2
-    if jp2.is_jp2(buf):   # a JPEG 2000 payload (LBDRN_BASE_CODEC=jp2, or the reference's own: decode.py:69-73)
-        x = jp2.decode(buf)
-        if keep_on_device:
-            from . import ops
-            return ops.to_device_u16(x.astype(np.uint16), device)
-        return x
+    if jp2.is_jp2(buf):   # a JPEG 2000 payload (LBDRN_BASE_CODEC=jp2 / jp2-gpu, or the reference's own: decode.py:69-73)
+        return _decode_jp2(buf, device, keep_on_device)
     if buf[:4] == BASE_LBB2_MAGIC:
         from . import ops
         code, C, H, W = struct.unpack_from(">BHII", buf, 4)
