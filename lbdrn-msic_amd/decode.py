@@ -4,7 +4,10 @@ integer reconstruction run as one fused HIP kernel (lbdrn_hip.codec.apply_image)
 
 Under `python -m torch.distributed.run --nproc-per-node N decode.py ...` the split_ratio tiles of the
 bitstream are decoded round-robin on N GPUs and merged on rank 0 (tiles are independent: no exchange
-while decoding)."""
+while decoding).
+
+`--window X0 Y0 W H` reconstructs that part of the scene only (lbdrn_hip.codec.decode_window): tiles the window does not
+touch are skipped by the byte sizes in the header, touched ones are decoded on a crop with a margin of D."""
 import argparse
 import os
 import random
@@ -50,13 +53,60 @@ def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True):
     return bitstream
 
 
+def decode_window_main(args, rank, world):
+    """`--window`: one part of the scene, bit-identical to that crop of the whole reconstruction.  Its records go to
+    decode_window.txt: decode.txt, the marker of a finished whole decode, is neither read nor written."""
+    dirname, basename = os.path.split(args.bin_path)
+    dirname = dirname or "."
+    if rank == 0:
+        logger.create_logger(dirname, "decode_window.txt")
+    else:
+        logger.create_logger(dirname, "", log_file_only=True)
+    logger.log.info(f"Binstream: {args.bin_path}")
+    start_time = time.time()
+    with open(args.bin_path, "rb") as fin:
+        bitstream = fin.read()
+    width, height = read_image_header(bitstream)[2:4]
+    x0, y0, w, h = codec.check_window(args.window, width, height)
+    logger.log.info(f"Window: x0={x0} y0={y0} w={w} h={h} of {width} x {height}")
+    # the touched tiles are dealt over the ranks like all tiles of a whole decode
+    _, parts = codec.decode_window_pieces(bitstream, args.window, device=DEVICE, take=lambda k, piece: k % world == rank)
+    parts = [(pc.ox, pc.oy, ops.from_device_u16(rec)) for pc, rec in parts]
+    gathered = shard.gather_to_root(parts) if world > 1 else [parts]
+    if rank == 0:
+        image = None
+        for ox, oy, rec in (rec for part in gathered for rec in part):
+            if image is None:
+                image = np.zeros((rec.shape[0], h, w), rec.dtype)
+            image[:, oy:oy + rec.shape[1], ox:ox + rec.shape[2]] = rec
+        recon_path = args.out_path or f"{dirname}/{basename[:-4]}_recon_x{x0}_y{y0}_w{w}_h{h}.tif"
+        write_tiff_with_gdal(recon_path, image)
+        logger.log.info(f"Recon: {recon_path}")
+        logger.log.info(f"Time elapsed: {time.time() - start_time}")
+        if args.org_path is not None:
+            org_img = raster_io.read_raster(args.org_path)
+            org_img = org_img.reshape((-1,) + org_img.shape[-2:])[:, y0:y0 + h, x0:x0 + w]
+            mse_value = np.mean((org_img.astype(np.float32) - image.astype(np.float32)) ** 2)
+            logger.log.info(f"MSE: {mse_value}")
+            logger.log.info(f"PSNR: {10 * np.log10(10000 ** 2 / mse_value)}")    # (no bpsp: a property of the whole file)
+    if world > 1:
+        shard.finish()
+    return 0
+
+
 def main(argv=None, shard_tiles=None):
     global K, D, bc, nl, DEVICE, ACTIVATION
     p = argparse.ArgumentParser(description="LBDRN-RSIC")
     p.add_argument("--seed", type=int, default=19920517)
     p.add_argument("-i", "--bin_path", type=str, help="binstream path")
     p.add_argument("-org", "--org_path", type=str, default=None, help="org path")
+    p.add_argument("--window", type=int, nargs=4, default=None, metavar=("X0", "Y0", "W", "H"),
+                   help="reconstruct this part of the scene only (scene pixels)")
+    p.add_argument("-o", "--out_path", type=str, default=None,
+                   help="with --window: where the raster goes (default <name>_recon_x{X0}_y{Y0}_w{W}_h{H}.tif)")
     args = p.parse_args(argv)
+    if args.out_path is not None and args.window is None:
+        p.error("-o names the raster of a --window decode")
     rank, world = 0, 1
     if shard_tiles is None:
         shard_tiles = shard.env_world()[1] > 1
@@ -66,6 +116,8 @@ def main(argv=None, shard_tiles=None):
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     random.seed(args.seed)
+    if args.window is not None:
+        return decode_window_main(args, rank, world)
     dirname, basename = os.path.split(args.bin_path)
     dirname = dirname or "."
     filename = os.path.splitext(basename)[0]

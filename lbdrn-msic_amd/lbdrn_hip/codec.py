@@ -4,6 +4,8 @@ fit_image() stands where the reference's encode.train() stands (ref encode.py:67
 apply_image() where decode.test()'s numeric core stands (ref decode.py:73-134); file handling,
 payload coding and logging stay in encode.py / decode.py.
 """
+import collections
+import copy
 import os
 import threading
 import time
@@ -684,3 +686,108 @@ def apply_image(base, params, K, D, base_channel, num_layers, cfg=None, device="
     if want_y:
         return ops.from_device_u16(out[0]), out[1].cpu().numpy()
     return ops.from_device_u16(out)
+
+
+# ---------------------------------------------------------------- a window of a scene (decode.py --window)
+
+WindowPiece = collections.namedtuple(
+    "WindowPiece", "tile tx ty tw th xa xb ya yb left right top bottom ox oy")
+WindowPiece.__doc__ = """The part of a window that lies in one tile.  tile: index in tile_windows order; (tx, ty, tw, th): the
+tile in scene pixels; [xa,xb) x [ya,yb): the window clipped to the tile, in TILE pixels; left / right / top / bottom: the
+margin of MSB samples taken around it (D, clipped to the tile's own edges); (ox, oy): where the piece goes in the window."""
+
+
+def check_window(window, width, height):
+    """(x0, y0, w, h) as ints; an empty window or one not inside the scene is a ValueError that names the scene size."""
+    try:
+        x0, y0, w, h = (int(v) for v in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"window {window!r}: four integers (x0, y0, w, h) expected") from None
+    if w < 1 or h < 1:
+        raise ValueError(f"window x0={x0} y0={y0} w={w} h={h} is empty (the scene is {width} x {height})")
+    if x0 < 0 or y0 < 0 or x0 + w > width or y0 + h > height:
+        raise ValueError(f"window x0={x0} y0={y0} w={w} h={h} is not inside the {width} x {height} scene")
+    return x0, y0, w, h
+
+
+def window_pieces(width, height, split_ratio, window, D):
+    """The tiles a window touches, in tile order, as WindowPieces (host arithmetic only).  The network is a per-pixel
+    function of the (2D+1)^2 MSB neighbourhood: a piece needs its own samples plus a margin of D.  Where the margin is cut
+    by the tile's edge the crop's edge IS the tile's edge and the kernels' reflect rule there equals the whole tile's
+    (ref LBDRNdataset.py:120); elsewhere the margin holds the true neighbours and its outputs are discarded."""
+    from LBDRNdataset import tile_windows
+    x0, y0, w, h = check_window(window, width, height)
+    pieces = []
+    for t, (_, _, tx, ty, tw, th) in enumerate(tile_windows(width, height, split_ratio)):
+        xa, xb = max(x0, tx) - tx, min(x0 + w, tx + tw) - tx
+        ya, yb = max(y0, ty) - ty, min(y0 + h, ty + th) - ty
+        if xa >= xb or ya >= yb:
+            continue
+        pieces.append(WindowPiece(t, tx, ty, tw, th, xa, xb, ya, yb, min(D, xa), min(D, tw - xb), min(D, ya),
+                                  min(D, th - yb), tx + xa - x0, ty + ya - y0))
+    return pieces
+
+
+def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, take=None):
+    """The pieces of decode_window(): -> (scene (width, height), [(WindowPiece, [C][yb-ya][xb-xa] device tensor), ...]).
+    take(k, piece) -> bool: which of the touched tiles (k counts them in tile order) this caller decodes (decode.py deals
+    them over its ranks); the others are skipped like the tiles the window does not touch."""
+    from . import container
+    from .features import window_tables
+    bitstream = bytes(bitstream) if not isinstance(bitstream, (bytes, memoryview)) else bitstream
+    n_hdr, split_ratio, width, height, K, bc, nl, D, nn_list, base_list = container.unpack_header(bitstream)
+    pieces = window_pieces(width, height, split_ratio, window, D)      # raises before any device work
+    cfg = copy.copy(cfg) if cfg is not None else FeatCfg.from_constants()
+    activation = container.header_activation(bitstream)
+    if activation is not None:                                         # the file says which network it holds (decode.py)
+        cfg.activation = activation
+    dev = torch.device(device)
+    offsets = [n_hdr]
+    for t in range(split_ratio * split_ratio):                         # a tile is reached without reading the ones before it
+        offsets.append(offsets[-1] + nn_list[t] + base_list[t])
+    out = []
+    for k, pc in enumerate(pieces):
+        if take is not None and not take(k, pc):
+            continue
+        off = offsets[pc.tile]
+        nn_payload = bitstream[off:off + nn_list[pc.tile]]
+        base_payload = bitstream[off + nn_list[pc.tile]:offsets[pc.tile + 1]]
+        # the MSB payload has no partial mode: decoded whole, cropped on the device
+        base = container.decode_base(bytes(base_payload), device=device, keep_on_device=True)
+        if not isinstance(base, torch.Tensor):
+            base = np.ascontiguousarray(base).astype(np.uint16)
+            base = ops.to_device_u16(base[None] if base.ndim == 2 else base, dev)
+        msb_d = base if base.dim() == 3 else base[None]
+        C, H, W = msb_d.shape
+        if (H, W) != (pc.th, pc.tw):
+            raise ValueError(f"tile {pc.tile}: the MSB payload is {W} x {H}, the header's tile is {pc.tw} x {pc.th}")
+        # MSB.max() of the WHOLE tile normalises every feature (ref LBDRNdataset.py:120, decode.py:93): never the crop's
+        msb_max = int((msb_d.to(torch.int32) & 0xFFFF).max().item())
+        need = ops.param_count(ops.make_net(cfg.feature_dim(C, D), bc, C, nl))
+        params = container.decode_weights(bytes(nn_payload), expected=need)
+        rows, cols = (pc.ya - pc.top, pc.yb + pc.bottom), (pc.xa - pc.left, pc.xb + pc.right)
+        crop = msb_d[:, rows[0]:rows[1], cols[0]:cols[1]].contiguous()
+        geom = ops.FeatureGeometry(C, rows[1] - rows[0], cols[1] - cols[0], K, D, msb_max, cfg, dev,
+                                   tables=window_tables(H, W, cfg, rows, cols))
+        net = ops.make_net(geom.F, bc, C, nl, cfg.act)
+        p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
+        rec = ops.decode_fused(geom, net, crop, p, path=path)
+        out.append((pc, rec[:, pc.top:pc.top + pc.yb - pc.ya, pc.left:pc.left + pc.xb - pc.xa]))
+    return (width, height), out
+
+
+def decode_window(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, keep_on_device=True):
+    """Reconstruct window = (x0, y0, w, h) (scene pixels) of the scene a .bin holds -> uint16 [C][h][w], bit-identical to
+    that crop of the whole reconstruction (decode.py), as a device tensor (uint16 bits in int16 storage, like every plane
+    here) or, with keep_on_device=False, as numpy.  Tiles the window does not touch are skipped by the byte sizes the header
+    lists: no weight stream, no MSB payload and no kernel runs for them.  A touched tile's MSB payload is decoded whole
+    and cropped with a margin of D (window_pieces); its maximum, K, D, the colour switches and the activation are the
+    tile's, and with USE_COORDINATES the crop brings the tile's table rows and columns (features.window_tables)."""
+    _, parts = decode_window_pieces(bitstream, window, device, path, cfg)
+    x0, y0, w, h = (int(v) for v in window)
+    out = None
+    for pc, rec in parts:
+        if out is None:
+            out = torch.empty((rec.shape[0], h, w), dtype=rec.dtype, device=rec.device)
+        out[:, pc.oy:pc.oy + rec.shape[1], pc.ox:pc.ox + rec.shape[2]] = rec
+    return out if keep_on_device else ops.from_device_u16(out)

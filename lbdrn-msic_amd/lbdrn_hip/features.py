@@ -62,3 +62,10 @@ def pos_tables(H, W, cfg):
     if cfg.P == 0:
         return np.zeros((H, 0), np.float32), np.zeros((W, 0), np.float32)
     return _axis_table(H, cfg), _axis_table(W, cfg)
+
+
+def window_tables(H, W, cfg, rows, cols):
+    """The tables of rows [rows[0], rows[1]) and columns [cols[0], cols[1]) of an H x W raster: pos_tables(H, W) sliced, never
+    pos_tables of the crop's own size -- a pixel of a crop keeps the coordinate it has in its raster (codec.decode_window)."""
+    rowtab, coltab = pos_tables(H, W, cfg)
+    return np.ascontiguousarray(rowtab[rows[0]:rows[1]]), np.ascontiguousarray(coltab[cols[0]:cols[1]])

@@ -44,11 +44,15 @@ def _u16(t):
 class FeatureGeometry:
     """lbdrn_geom plus the device tables it points at (kept alive here)."""
 
-    def __init__(self, C, H, W, K, D, msb_max, cfg, device):
+    def __init__(self, C, H, W, K, D, msb_max, cfg, device, tables=None):
+        """tables: the host tables ([H,P], [W,P]) instead of pos_tables(H, W, cfg) -- a crop of a larger raster brings the
+        rows and columns of that raster's tables (features.window_tables), so that each pixel keeps its coordinate."""
         from .features import pos_tables
         self.C, self.H, self.W, self.K, self.D, self.msb_max = C, H, W, K, D, int(msb_max)
         self.cfg = cfg
-        rowtab, coltab = pos_tables(H, W, cfg)
+        rowtab, coltab = tables if tables is not None else pos_tables(H, W, cfg)
+        if rowtab.shape != (H, cfg.P) or coltab.shape != (W, cfg.P):
+            raise ValueError(f"positional tables {rowtab.shape}, {coltab.shape} for a {H} x {W} raster with P = {cfg.P}")
         self.P = rowtab.shape[1]
         self.rowtab = torch.from_numpy(rowtab).to(device) if self.P else None
         self.coltab = torch.from_numpy(coltab).to(device) if self.P else None
