@@ -1,16 +1,19 @@
 /* liblbdrn_jp2k_dec.so -- the GPU decoder of the lossless JPEG 2000 MSB payload (csrc/jp2k_dec.hip), plain C ABI.
  *
- * Reads what lbdrn_jp2k_encode (include/lbdrn_hip.h) writes and what OpenJPEG (GDAL's JP2OpenJPEG driver, this package's
- * liblbdrn_jp2.so) and Pillow write with reversible settings, without OpenJPEG: the host parses boxes, headers and packet
- * headers into a validated table of code blocks, the device decodes the blocks (T.800 Annexes C, D), undoes the 5/3
- * wavelet (Annex F) and the DC shift, and leaves the planes in HBM, as lbdrn_plane_decode leaves LBB2's.
+ * Reads what lbdrn_jp2k_encode (include/lbdrn_hip.h) writes and what OpenJPEG (this package's liblbdrn_jp2.so) and Pillow
+ * write with reversible settings, without OpenJPEG: the host parses boxes, headers and packet headers into a validated
+ * table of code blocks, the device decodes the blocks (T.800 Annexes C, D), undoes the 5/3 wavelet (Annex F), the
+ * reversible component transform where the file has one (G.2) and the DC shift, and leaves the planes in HBM, as
+ * lbdrn_plane_decode leaves LBB2's.
  *
  * Accepted: a .jp2 file or a raw codestream with unsigned components of one depth of 1..16 bits, all of the image's size,
- * any tile size, reversible 5/3 with 0..16 decompositions, no component transform, one quality layer, LRCP, code blocks
- * up to 64 x 64 of style 0, default precincts, no quantisation, SOP / EPH present or absent, several tile-parts per tile,
- * COM / TLM / PLT / PLM / CRG segments (skipped).  Anything else -- 9/7, several layers, other block styles, precinct
- * partitions, signed or sub-sampled components, PPM / PPT, COC / QCC / RGN / POC -- is LBDRN_E_UNSUPPORTED with a message
- * that names the feature, before anything is launched.
+ * any tile size, reversible 5/3 with 0..16 decompositions, no component transform or the reversible one (RCT; on
+ * components 0 - 2 of three or more), one quality layer, LRCP, code blocks up to 64 x 64 of style 0, default precincts or
+ * a precinct partition (one size per resolution in COD, down to exponent 0 at the lowest resolution; at most 2^20
+ * precincts per resolution of a tile), no quantisation, SOP / EPH present or absent, several tile-parts per tile,
+ * COM / TLM / PLT / PLM / CRG segments (skipped).  Anything else -- 9/7, several layers, other progression orders, other
+ * block styles, the component transform on fewer than three components, signed or sub-sampled components, PPM / PPT,
+ * COC / QCC / RGN / POC -- is LBDRN_E_UNSUPPORTED with a message that names the feature, before anything is launched.
  *
  * Conventions are those of lbdrn_hip.h: every call returns 0 or a negative lbdrn_status (the same values),
  * lbdrn_jp2kd_last_error() returns a per-thread message for the last failure, the library reads no environment variable

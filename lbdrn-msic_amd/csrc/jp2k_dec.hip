@@ -1,6 +1,6 @@
 // liblbdrn_jp2k_dec.so (include/lbdrn_jp2k_dec.h): the decoder of the lossless JPEG 2000 MSB payload -- what jp2k.hip
-// writes, what OpenJPEG / GDAL's JP2OpenJPEG driver and Pillow write with reversible settings -- with the planes left
-// in HBM.  The host parses the file into a validated table of code blocks (jp2k_t2d.inc); tier-1 and the wavelet, which
+// writes, what OpenJPEG and Pillow write with reversible settings, precinct partitions and the reversible component
+// transform included -- with the planes left in HBM.  The host parses the file into a validated table of code blocks (jp2k_t2d.inc); tier-1 and the wavelet, which
 // are independent per block and per sample, run here:
 //
 //   k_jp2k_unblocks   one wave per code block: the wave zeroes the block's LDS state, lane 0 runs the serial decoder of
@@ -13,7 +13,10 @@
 //                     neighbours), symmetric extension by mirrored indices, the parity of the line's first coordinate
 //                     from the tile's place on the grid -- no thread waits for another; rows before columns, from the
 //                     lowest resolution up (the reverse of F.4.2's analysis order)
-//   k_jp2k_unshift    DC shift back, clamp to [0, 2^bits - 1] (G.1.2), uint16 into [C][H][W]
+//   k_jp2k_unshift    DC shift back, clamp to [0, 2^bits - 1] (G.1.2), uint16 into [C][H][W]; its RCT form (files with
+//                     the reversible component transform, COD's mct = 1) first undoes the transform on components 0 - 2
+//                     (G.2.2): every thread of those three reads the three slabs at its sample and keeps its own
+//                     component's value -- still one thread per stored sample, and no thread waits for another
 //
 // The device only ever indexes with what the host has checked: block rectangles inside the slab, offset + length inside
 // the file.  The kernels clamp once more.
@@ -135,15 +138,28 @@ __global__ __launch_bounds__(256) void k_jp2k_unlift(const int32_t* __restrict__
     dst[(size_t)slab * g.slab + (size_t)oy * g.tw + ox] = out;
 }
 
+// RCT: g.C >= 3 (the host refuses the transform on fewer components).  A damaged file can leave any int32 in a slab: the
+// transform's sums wrap around as unsigned ones, the floor is taken of a 64-bit sum, the shift is added in 64 bits.
+template <bool RCT>
 __global__ __launch_bounds__(256) void k_jp2k_unshift(const int32_t* __restrict__ A, Jp2kdDev g, int bits, uint16_t* __restrict__ planes)
 {
     const int slab = blockIdx.z, c = slab % g.C, tile = slab / g.C;
     const int64_t x0 = (int64_t)(tile % g.ntx) * g.XT, y0 = (int64_t)(tile / g.ntx) * g.YT;
     const int lx = blockIdx.x * 256 + threadIdx.x, ly = blockIdx.y;
     if (lx >= g.tw || x0 + lx >= g.W || y0 + ly >= g.H) return;
-    int v = A[(size_t)slab * g.slab + (size_t)ly * g.tw + lx] + (1 << (bits - 1));
     const int top = (1 << bits) - 1;
-    v = v < 0 ? 0 : (v > top ? top : v);
+    int v;
+    if (RCT && c < 3) {
+        const int32_t* Y = A + (size_t)(slab - c) * g.slab + (size_t)ly * g.tw + lx;      // the tile's component 0
+        const int32_t y0v = Y[0], y1v = Y[g.slab], y2v = Y[2 * g.slab];
+        const uint32_t i1 = (uint32_t)y0v - (uint32_t)(((int64_t)y1v + y2v) >> 2);        // (G-6; >> of a negative sum: the floor)
+        const uint32_t u = c == 1 ? i1 : (uint32_t)(c == 0 ? y2v : y1v) + i1;             // (G-7, G-8)
+        const int64_t w = (int64_t)(int32_t)u + (1 << (bits - 1));
+        v = (int)(w < 0 ? 0 : (w > top ? top : w));
+    } else {
+        v = A[(size_t)slab * g.slab + (size_t)ly * g.tw + lx] + (1 << (bits - 1));
+        v = v < 0 ? 0 : (v > top ? top : v);
+    }
     planes[((size_t)c * g.H + (size_t)(y0 + ly)) * g.W + (size_t)(x0 + lx)] = (uint16_t)v;
 }
 
@@ -259,7 +275,8 @@ static int jp2kd_decode(const void* buf, size_t n, uint16_t* planes, int C, int 
     }
     {
         const dim3 grid((unsigned)((p.tw + 255) / 256), (unsigned)p.th, slabs);
-        k_jp2k_unshift<<<grid, 256, 0, s>>>(p.NL ? w.L : w.A, g, p.bits, planes);
+        if (p.mct) k_jp2k_unshift<true><<<grid, 256, 0, s>>>(p.NL ? w.L : w.A, g, p.bits, planes);
+        else k_jp2k_unshift<false><<<grid, 256, 0, s>>>(p.NL ? w.L : w.A, g, p.bits, planes);
         LBDRN_LAUNCH_CHECK();
     }
     LBDRN_HIP_TRY(hipStreamSynchronize(s));     // (the host copies above were staged from memory this call owns)

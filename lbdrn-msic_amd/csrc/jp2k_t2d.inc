@@ -5,9 +5,16 @@
 // jp2k_dec.hip; Band is jp2k_t2.inc's.
 //
 // Accepted: unsigned components of one depth of 1..16 bits without sub-sampling, any tile size, reversible 5/3 with up to
-// DEC_MAX_LEVELS decompositions, no component transform, one layer, LRCP, code blocks up to 64 x 64 of style 0, default
-// precincts (and no resolution of a tile that spans two of them), no quantisation, SOP / EPH, several tile-parts per
-// tile, COM / TLM / PLT / PLM / CRG skipped.  Everything else is DEC_UNSUPPORTED with the feature named.
+// DEC_MAX_LEVELS decompositions, no component transform or the reversible one (RCT, on three components or more), one
+// layer, LRCP, code blocks up to 64 x 64 of style 0, default precincts or a precinct partition (one size per resolution
+// in COD, up to DEC_MAX_PRECINCTS precincts per resolution of a tile), no quantisation, SOP / EPH, several tile-parts
+// per tile, COM / TLM / PLT / PLM / CRG skipped.  Everything else is DEC_UNSUPPORTED with the feature named.
+//
+// Precincts (B.6, B.7): the precinct grid of a resolution of a tile is anchored at 0 in the resolution's coordinates; in
+// a band above the lowest resolution a precinct spans half its size; a code block never exceeds a precinct, so the
+// block exponents of a resolution are min(COD's, PP - 1) (min(COD's, PP) at the lowest).  Precinct and block boundaries
+// coincide, so a band's blocks are those of its own zero-anchored grid whatever the partition: it only decides which
+// packet carries a block, and over which sub-grid that packet's tag trees are built.
 //
 // Every offset and length is checked against the buffer before it is used: all reads go through Bytes, which answers 0
 // beyond the end and remembers that it was asked.  What the device gets is a table that satisfies, per block,
@@ -28,6 +35,7 @@ enum { DEC_OK = 0, DEC_BAD = -1, DEC_UNSUPPORTED = -3 };   // the values of LBDR
 constexpr int DEC_MAX_LEVELS = 16;
 constexpr int64_t DEC_MAX_BLOCKS = (int64_t)1 << 24;
 constexpr int64_t DEC_MAX_SAMPLES = (int64_t)1 << 33;
+constexpr int64_t DEC_MAX_PRECINCTS = (int64_t)1 << 20;    // per resolution of a tile
 
 struct DecError {
     int code;
@@ -57,6 +65,8 @@ struct DecParams {
     int XT, YT;            // tile size; image and tile grid start at (0, 0)
     int NL;                // decompositions
     int cbw, cbh;
+    int mct;               // 1: the reversible component transform on components 0 - 2
+    int ppx[DEC_MAX_LEVELS + 1], ppy[DEC_MAX_LEVELS + 1];   // precinct exponents per resolution, from the lowest (15: default)
     int guard;
     int eps[1 + 3 * 32];   // exponents: LL, then HL LH HH of each resolution from the lowest
     int sop, eph;
@@ -68,8 +78,9 @@ struct DecStream {
     std::vector<std::vector<DecSegment>> parts;   // per tile, in the order of the codestream
 };
 
-struct DecBlock {      // one code block, in the order the packets carry them: tile, resolution, component, band, raster
-    int32_t tile, comp, res, band, gx, gy;
+struct DecBlock {      // one code block, in the order the packets carry them: tile, resolution, component, precinct, band, raster
+    int32_t tile, comp, res, band, gx, gy;      // gx, gy: in the band's block grid
+    int32_t prec;                // its precinct, in raster order of the resolution's precinct grid
     int32_t numbps, passes;      // passes 0: the file does not include the block (its coefficients are zero)
     int64_t offset;              // of its bytes in the file; -1 when not included
     int32_t length, mb;
@@ -88,16 +99,33 @@ inline void dec_tile_rect(const DecParams& p, int t, int64_t* x0, int64_t* y0, i
     *y1 = *y0 + p.YT < p.H ? *y0 + p.YT : p.H;
 }
 
-// The bands of resolution r of tile t (B-14, B-15); 0 when the resolution is empty and has no packet, -1 when it spans
-// more than one default precinct (2^15 samples).
-inline int dec_bands(const DecParams& p, int t, int r, Band bd[3])
+struct DecRes {        // one resolution of one tile: its bands, its code-block size and its precinct grid
+    int nbands;        // 0: the resolution is empty and has no packet
+    Band bd[3];        // gw, gh: the band's whole block grid
+    int cbw, cbh;      // code blocks here: COD's, cut down to a precinct's span in the bands (B.7)
+    int pbx, pby;      // exponents of a precinct's span in the bands' coordinates: PP - 1, PP at the lowest resolution
+    int64_t px0, py0;  // the precinct grid's first column and row, counted from the origin
+    int64_t npx, npy;  // precincts across and down (B-16)
+};
+
+// The bands of resolution r of tile t (B-14, B-15) and its precinct grid; returns the number of bands.
+inline int dec_bands(const DecParams& p, int t, int r, DecRes* rs)
 {
+    Band* bd = rs->bd;
+    rs->nbands = 0;
+    rs->npx = rs->npy = 0;
     int64_t x0, y0, x1, y1;
     dec_tile_rect(p, t, &x0, &y0, &x1, &y1);
     const int64_t s = (int64_t)1 << (p.NL - r);
     const int64_t rx0 = dec_cdiv(x0, s), rx1 = dec_cdiv(x1, s), ry0 = dec_cdiv(y0, s), ry1 = dec_cdiv(y1, s);
     if (rx1 <= rx0 || ry1 <= ry0) return 0;
-    if ((rx0 >> 15) != ((rx1 - 1) >> 15) || (ry0 >> 15) != ((ry1 - 1) >> 15)) return -1;
+    const int ppx = p.ppx[r], ppy = p.ppy[r];
+    rs->pbx = r == 0 ? ppx : ppx - 1; rs->pby = r == 0 ? ppy : ppy - 1;       // (dec_read_headers: PP >= 1 above r = 0)
+    rs->cbw = p.cbw < (1 << rs->pbx) ? p.cbw : 1 << rs->pbx;
+    rs->cbh = p.cbh < (1 << rs->pby) ? p.cbh : 1 << rs->pby;
+    rs->px0 = rx0 >> ppx; rs->py0 = ry0 >> ppy;
+    rs->npx = ((rx1 + ((int64_t)1 << ppx) - 1) >> ppx) - rs->px0;
+    rs->npy = ((ry1 + ((int64_t)1 << ppy) - 1) >> ppy) - rs->py0;
     const int n = r == 0 ? 1 : 3;
     const int nb = r == 0 ? p.NL : p.NL - r + 1;
     const int64_t lx0 = dec_cdiv(rx0, 2), lx1 = dec_cdiv(rx1, 2), ly0 = dec_cdiv(ry0, 2), ly1 = dec_cdiv(ry1, 2);
@@ -114,36 +142,62 @@ inline int dec_bands(const DecParams& p, int t, int r, Band bd[3])
         q.y = r == 0 ? 0 : (yo ? (int)(ly1 - ly0) : 0);
         if (q.w <= 0 || q.h <= 0) q.gw = q.gh = 0;
         else {
-            q.gw = (int)(dec_cdiv(bx1, p.cbw) - dec_fdiv(bx0, p.cbw));
-            q.gh = (int)(dec_cdiv(by1, p.cbh) - dec_fdiv(by0, p.cbh));
+            q.gw = (int)(dec_cdiv(bx1, rs->cbw) - dec_fdiv(bx0, rs->cbw));
+            q.gh = (int)(dec_cdiv(by1, rs->cbh) - dec_fdiv(by0, rs->cbh));
         }
         q.mb = p.guard + p.eps[r == 0 ? 0 : 1 + 3 * (r - 1) + b] - 1;   // (E-2)
         q.first = 0;
     }
+    rs->nbands = n;
     return n;
 }
 
-inline void dec_block_rect(const DecParams& p, const Band& q, int gx, int gy, int* x, int* y, int* w, int* h)
+// The blocks of band b that lie in precinct (px, py) of the resolution's grid: a rectangle of the band's block grid, from
+// (*gx0, *gy0), *gw x *gh blocks; 0 x 0 when the precinct holds nothing of the band.
+inline void dec_precinct_blocks(const DecRes& rs, int b, int64_t px, int64_t py, int* gx0, int* gy0, int* gw, int* gh)
 {
-    const int64_t cx0 = (dec_fdiv(q.bx0, p.cbw) + gx) * p.cbw, cy0 = (dec_fdiv(q.by0, p.cbh) + gy) * p.cbh;
+    const Band& q = rs.bd[b];
+    *gx0 = *gy0 = *gw = *gh = 0;
+    if (q.w <= 0 || q.h <= 0) return;
+    const int64_t bx1 = (int64_t)q.bx0 + q.w, by1 = (int64_t)q.by0 + q.h;
+    const int64_t cx0 = (rs.px0 + px) << rs.pbx, cx1 = (rs.px0 + px + 1) << rs.pbx;
+    const int64_t cy0 = (rs.py0 + py) << rs.pby, cy1 = (rs.py0 + py + 1) << rs.pby;
+    const int64_t ax0 = cx0 > q.bx0 ? cx0 : q.bx0, ax1 = cx1 < bx1 ? cx1 : bx1;
+    const int64_t ay0 = cy0 > q.by0 ? cy0 : q.by0, ay1 = cy1 < by1 ? cy1 : by1;
+    if (ax1 <= ax0 || ay1 <= ay0) return;
+    *gx0 = (int)(dec_fdiv(ax0, rs.cbw) - dec_fdiv(q.bx0, rs.cbw));
+    *gy0 = (int)(dec_fdiv(ay0, rs.cbh) - dec_fdiv(q.by0, rs.cbh));
+    *gw = (int)(dec_cdiv(ax1, rs.cbw) - dec_fdiv(ax0, rs.cbw));
+    *gh = (int)(dec_cdiv(ay1, rs.cbh) - dec_fdiv(ay0, rs.cbh));
+}
+
+inline void dec_block_rect(const DecRes& rs, const Band& q, int gx, int gy, int* x, int* y, int* w, int* h)
+{
+    const int64_t cx0 = (dec_fdiv(q.bx0, rs.cbw) + gx) * rs.cbw, cy0 = (dec_fdiv(q.by0, rs.cbh) + gy) * rs.cbh;
     const int64_t ax0 = cx0 > q.bx0 ? cx0 : q.bx0, ay0 = cy0 > q.by0 ? cy0 : q.by0;
-    const int64_t ax1 = cx0 + p.cbw < (int64_t)q.bx0 + q.w ? cx0 + p.cbw : (int64_t)q.bx0 + q.w;
-    const int64_t ay1 = cy0 + p.cbh < (int64_t)q.by0 + q.h ? cy0 + p.cbh : (int64_t)q.by0 + q.h;
+    const int64_t ax1 = cx0 + rs.cbw < (int64_t)q.bx0 + q.w ? cx0 + rs.cbw : (int64_t)q.bx0 + q.w;
+    const int64_t ay1 = cy0 + rs.cbh < (int64_t)q.by0 + q.h ? cy0 + rs.cbh : (int64_t)q.by0 + q.h;
     *x = q.x + (int)(ax0 - q.bx0); *y = q.y + (int)(ay0 - q.by0);
     *w = (int)(ax1 - ax0); *h = (int)(ay1 - ay0);
 }
 
-// the number of code blocks, or a negative code (a resolution beyond one precinct, more blocks than DEC_MAX_BLOCKS)
+// the number of code blocks, or a negative code (more precincts in a resolution of a tile than DEC_MAX_PRECINCTS, more
+// blocks than DEC_MAX_BLOCKS).  A band's blocks are counted from its own grid: the precincts partition it.
 inline int64_t dec_count_blocks(const DecParams& p, DecError* e)
 {
     int64_t n = 0;
     for (int t = 0; t < p.ntx * p.nty; ++t)
         for (int r = 0; r <= p.NL; ++r) {
-            Band bd[3];
-            const int nbands = dec_bands(p, t, r, bd);
-            if (nbands < 0) return e->fail(DEC_UNSUPPORTED, "precinct partition: resolution %d of tile %d spans more than one default precinct", r, t);
-            for (int b = 0; b < nbands; ++b) n += (int64_t)bd[b].gw * bd[b].gh * p.C;
-            if (n > DEC_MAX_BLOCKS) return e->fail(DEC_UNSUPPORTED, "more than %lld code blocks", (long long)DEC_MAX_BLOCKS);
+            DecRes rs;
+            const int nbands = dec_bands(p, t, r, &rs);
+            if (rs.npx > DEC_MAX_PRECINCTS || rs.npy > DEC_MAX_PRECINCTS || rs.npx * rs.npy > DEC_MAX_PRECINCTS)
+                return e->fail(DEC_UNSUPPORTED, "precinct partition: resolution %d of tile %d has %lld x %lld precincts (at most %lld)", r, t,
+                               (long long)rs.npx, (long long)rs.npy, (long long)DEC_MAX_PRECINCTS);
+            for (int b = 0; b < nbands; ++b) {
+                const int64_t m = (int64_t)rs.bd[b].gw * rs.bd[b].gh;
+                if (m <= DEC_MAX_BLOCKS) n += m * p.C;
+                if (m > DEC_MAX_BLOCKS || n > DEC_MAX_BLOCKS) return e->fail(DEC_UNSUPPORTED, "more than %lld code blocks", (long long)DEC_MAX_BLOCKS);
+            }
         }
     return n;
 }
@@ -207,13 +261,20 @@ inline int dec_read_headers(const uint8_t* f, size_t n, DecStream* s, DecError* 
         } else if (marker == 0xFF52) {
             if (len < 12) return e->fail(DEC_BAD, "short COD");
             const unsigned scod = cs.u8(q);
-            if (scod & 1) return e->fail(DEC_UNSUPPORTED, "precinct partition: explicit precinct sizes are not supported");
             p.sop = (scod >> 1) & 1; p.eph = (scod >> 2) & 1;
             if (cs.u8(q + 1) != 0) return e->fail(DEC_UNSUPPORTED, "progression order %u is not supported (LRCP only)", cs.u8(q + 1));
             if (cs.u16(q + 2) != 1) return e->fail(DEC_UNSUPPORTED, "%u quality layers are not supported (one only)", cs.u16(q + 2));
-            if (cs.u8(q + 4) != 0) return e->fail(DEC_UNSUPPORTED, "the multiple component transform is not supported");
+            if (cs.u8(q + 4) > 1) return e->fail(DEC_UNSUPPORTED, "multiple component transform %u is not supported (0 or 1)", cs.u8(q + 4));
+            p.mct = (int)cs.u8(q + 4);
             p.NL = (int)cs.u8(q + 5);
             if (p.NL > DEC_MAX_LEVELS) return e->fail(DEC_UNSUPPORTED, "%d decompositions (at most %d)", p.NL, DEC_MAX_LEVELS);
+            if ((scod & 1) && len < 12u + (unsigned)p.NL + 1)
+                return e->fail(DEC_UNSUPPORTED, "precinct partition: COD of %u bytes does not hold the %d precinct sizes it announces", len, p.NL + 1);
+            for (int r = 0; r <= p.NL; ++r) {      // lowest resolution first; PPx in the low nibble
+                p.ppx[r] = (scod & 1) ? (int)(cs.u8(q + 10 + r) & 15) : 15;
+                p.ppy[r] = (scod & 1) ? (int)(cs.u8(q + 10 + r) >> 4) : 15;
+                if (r > 0 && (p.ppx[r] == 0 || p.ppy[r] == 0)) return e->fail(DEC_BAD, "precinct exponent 0 at resolution %d", r);
+            }
             if (cs.u8(q + 6) > 4 || cs.u8(q + 7) > 4) return e->fail(DEC_UNSUPPORTED, "code blocks larger than 64 x 64 are not supported");
             p.cbw = 1 << (cs.u8(q + 6) + 2); p.cbh = 1 << (cs.u8(q + 7) + 2);
             if (cs.u8(q + 8) != 0) return e->fail(DEC_UNSUPPORTED, "code-block style %u is not supported (0 only)", cs.u8(q + 8));
@@ -233,6 +294,7 @@ inline int dec_read_headers(const uint8_t* f, size_t n, DecStream* s, DecError* 
         at += 2 + (size_t)len;
     }
     if (!have_siz || !have_cod || have_qcd < 0) return e->fail(DEC_BAD, "SIZ, COD or QCD missing");
+    if (p.mct && p.C < 3) return e->fail(DEC_UNSUPPORTED, "the component transform on %d components is not supported (T.800 has it on three)", p.C);
     if (have_qcd < 1 + 3 * p.NL) return e->fail(DEC_BAD, "QCD has %d exponents for %d bands", have_qcd, 1 + 3 * p.NL);
     for (int k = 0; k < 1 + 3 * p.NL; ++k)
         if (p.guard + p.eps[k] - 1 > 31) return e->fail(DEC_UNSUPPORTED, "%d magnitude bit-planes (at most 31)", p.guard + p.eps[k] - 1);
@@ -428,51 +490,58 @@ inline int dec_parse(const uint8_t* f, size_t n, const DecStream& s, std::vector
         if (end > n || at > end) return e->fail(DEC_BAD, "tile %d: its tile-part lies beyond the buffer", t);
         for (int r = 0; r <= p.NL; ++r)
             for (int c = 0; c < p.C; ++c) {
-                Band bd[3];
-                const int nbands = dec_bands(p, t, r, bd);
+                DecRes rs;
+                const int nbands = dec_bands(p, t, r, &rs);
                 if (nbands <= 0) continue;
-                while (at == end && seg + 1 < segs.size()) {      // the next tile-part of this tile
-                    ++seg;
-                    at = segs[seg].at; end = segs[seg].end;
-                    if (end > n || at > end) return e->fail(DEC_BAD, "tile %d: its tile-part lies beyond the buffer", t);
-                }
-                int32_t gw[3], gh[3], mb[3];
-                int64_t nblk = 0;
-                for (int b = 0; b < nbands; ++b) { gw[b] = bd[b].gw; gh[b] = bd[b].gh; mb[b] = bd[b].mb; nblk += (int64_t)gw[b] * gh[b]; }
-                if (p.sop && end - at >= 6 && in.u16(at) == 0xFF91) at += 6;
-                r3.assign((size_t)(nblk ? nblk : 1) * 3, 0);
-                const int64_t used = dec_packet_header(f + at, end - at, nbands, gw, gh, mb, r3.data());
-                if (used < 0) return e->fail(DEC_BAD, "tile %d, resolution %d, component %d: the packet header runs beyond its tile-part", t, r, c);
-                at += (size_t)used;
-                if (at > end) return e->fail(DEC_BAD, "tile %d: a packet header runs beyond its tile-part", t);
-                if (p.eph) {
-                    if (end - at < 2 || in.u16(at) != 0xFF92) return e->fail(DEC_BAD, "tile %d, resolution %d, component %d: EPH missing", t, r, c);
-                    at += 2;
-                }
-                int64_t i = 0;
-                for (int b = 0; b < nbands; ++b)
-                    for (int gy = 0; gy < bd[b].gh; ++gy)
-                        for (int gx = 0; gx < bd[b].gw; ++gx, ++i) {
-                            DecBlock k;
-                            memset(&k, 0, sizeof k);
-                            k.tile = t; k.comp = c; k.res = r; k.band = b; k.gx = gx; k.gy = gy;
-                            k.mb = bd[b].mb; k.orient = bd[b].orient;
-                            dec_block_rect(p, bd[b], gx, gy, &k.x, &k.y, &k.w, &k.h);
-                            k.passes = r3[(size_t)(3 * i)]; k.numbps = r3[(size_t)(3 * i + 1)]; k.length = r3[(size_t)(3 * i + 2)];
-                            k.offset = -1;
-                            if (k.w < 1 || k.h < 1 || k.w > 64 || k.h > 64 || k.x < 0 || k.y < 0 || k.x + k.w > p.tw || k.y + k.h > p.th)
-                                return e->fail(DEC_BAD, "tile %d: a code block of %d x %d at (%d, %d)", t, k.w, k.h, k.x, k.y);
-                            if (k.passes) {
-                                if (k.mb < 0 || k.mb > 31 || k.numbps < 1 || k.numbps > k.mb || k.passes < 1 || k.passes > 3 * k.numbps - 2)
-                                    return e->fail(DEC_BAD, "tile %d, resolution %d, component %d: a block of %d passes in %d of %d bit-planes",
-                                                   t, r, c, k.passes, k.numbps, k.mb);
-                                if (k.length < 0 || (size_t)k.length > end - at)
-                                    return e->fail(DEC_BAD, "tile %d: block data runs beyond the tile-part", t);
-                                k.offset = (int64_t)at;
-                                at += (size_t)k.length;
+                const Band* bd = rs.bd;
+                for (int64_t pr = 0; pr < rs.npx * rs.npy; ++pr) {      // one packet per precinct, with or without blocks
+                    while (at == end && seg + 1 < segs.size()) {      // the next tile-part of this tile
+                        ++seg;
+                        at = segs[seg].at; end = segs[seg].end;
+                        if (end > n || at > end) return e->fail(DEC_BAD, "tile %d: its tile-part lies beyond the buffer", t);
+                    }
+                    int32_t gx0[3], gy0[3], gw[3], gh[3], mb[3];
+                    int64_t nblk = 0;
+                    for (int b = 0; b < nbands; ++b) {
+                        dec_precinct_blocks(rs, b, pr % rs.npx, pr / rs.npx, &gx0[b], &gy0[b], &gw[b], &gh[b]);
+                        mb[b] = bd[b].mb;
+                        nblk += (int64_t)gw[b] * gh[b];
+                    }
+                    if (p.sop && end - at >= 6 && in.u16(at) == 0xFF91) at += 6;
+                    r3.assign((size_t)(nblk ? nblk : 1) * 3, 0);
+                    const int64_t used = dec_packet_header(f + at, end - at, nbands, gw, gh, mb, r3.data());
+                    if (used < 0) return e->fail(DEC_BAD, "tile %d, resolution %d, component %d: the packet header runs beyond its tile-part", t, r, c);
+                    at += (size_t)used;
+                    if (at > end) return e->fail(DEC_BAD, "tile %d: a packet header runs beyond its tile-part", t);
+                    if (p.eph) {
+                        if (end - at < 2 || in.u16(at) != 0xFF92) return e->fail(DEC_BAD, "tile %d, resolution %d, component %d: EPH missing", t, r, c);
+                        at += 2;
+                    }
+                    int64_t i = 0;
+                    for (int b = 0; b < nbands; ++b)
+                        for (int gy = gy0[b]; gy < gy0[b] + gh[b]; ++gy)
+                            for (int gx = gx0[b]; gx < gx0[b] + gw[b]; ++gx, ++i) {
+                                DecBlock k;
+                                memset(&k, 0, sizeof k);
+                                k.tile = t; k.comp = c; k.res = r; k.band = b; k.gx = gx; k.gy = gy; k.prec = (int32_t)pr;
+                                k.mb = bd[b].mb; k.orient = bd[b].orient;
+                                dec_block_rect(rs, bd[b], gx, gy, &k.x, &k.y, &k.w, &k.h);
+                                k.passes = r3[(size_t)(3 * i)]; k.numbps = r3[(size_t)(3 * i + 1)]; k.length = r3[(size_t)(3 * i + 2)];
+                                k.offset = -1;
+                                if (k.w < 1 || k.h < 1 || k.w > 64 || k.h > 64 || k.x < 0 || k.y < 0 || k.x + k.w > p.tw || k.y + k.h > p.th)
+                                    return e->fail(DEC_BAD, "tile %d: a code block of %d x %d at (%d, %d)", t, k.w, k.h, k.x, k.y);
+                                if (k.passes) {
+                                    if (k.mb < 0 || k.mb > 31 || k.numbps < 1 || k.numbps > k.mb || k.passes < 1 || k.passes > 3 * k.numbps - 2)
+                                        return e->fail(DEC_BAD, "tile %d, resolution %d, component %d: a block of %d passes in %d of %d bit-planes",
+                                                       t, r, c, k.passes, k.numbps, k.mb);
+                                    if (k.length < 0 || (size_t)k.length > end - at)
+                                        return e->fail(DEC_BAD, "tile %d: block data runs beyond the tile-part", t);
+                                    k.offset = (int64_t)at;
+                                    at += (size_t)k.length;
+                                }
+                                out->push_back(k);
                             }
-                            out->push_back(k);
-                        }
+                }
             }
         if (at != end || seg + 1 != segs.size())
             return e->fail(DEC_BAD, "tile %d: %zu bytes of its tile-parts are not accounted for", t, end - at);

@@ -1,6 +1,7 @@
 """ctypes binding of liblbdrn_jp2k_dec.so (include/lbdrn_jp2k_dec.h): the GPU decoder of the lossless JPEG 2000 MSB payload
-(csrc/jp2k_dec.hip).  Reads what `jp2-gpu` writes and what OpenJPEG / GDAL and Pillow write with reversible settings,
-without OpenJPEG, and leaves the planes in HBM.  Built by csrc/build.py beside liblbdrn_hip.so; LBDRN_JP2K_DEC_LIB
+(csrc/jp2k_dec.hip).  Reads what `jp2-gpu` writes and what OpenJPEG and Pillow write with reversible settings,
+without OpenJPEG, and leaves the planes in HBM.  Files with a precinct partition (COD's Scod bit 0) and with the
+reversible component transform (mct = 1 on three components or more) are read as well.  Built by csrc/build.py beside liblbdrn_hip.so; LBDRN_JP2K_DEC_LIB
 names another file."""
 import ctypes
 import os

@@ -9,4 +9,7 @@ set -u
 cd "$(dirname "$0")/.."
 ASAN=$(g++ -print-file-name=libasan.so)
 LBDRN_JP2K_DEC_SHIM_SANITIZE=1 LD_PRELOAD="$ASAN${LD_PRELOAD:+:$LD_PRELOAD}" ASAN_OPTIONS=detect_leaks=0 \
-  python -m pytest tests/test_jp2k_dec_host.py -x -q -m "not gpu" -k "block_decoder or packet_header or block_table or tile_parts or truncated"
+  python -m pytest tests/test_jp2k_dec_host.py -x -q -m "not gpu" -k "block_decoder or packet_header or block_table or tile_parts or truncated" || exit 1
+# the same for files with a precinct partition and the component transform (Pillow's, tests/golden/jp2k_precincts.npz)
+LBDRN_JP2K_DEC_SHIM_SANITIZE=1 LD_PRELOAD="$ASAN${LD_PRELOAD:+:$LD_PRELOAD}" ASAN_OPTIONS=detect_leaks=0 \
+  python -m pytest tests/test_jp2k_dec_precincts_host.py -x -q -m "not gpu" -k "not pillow_writes"
