@@ -7,8 +7,9 @@
 //   k_jp2k_lift     one direction of one 5/3 decomposition: every thread computes ONE output coefficient from the five
 //                   (three) inputs it depends on, symmetric extension by mirrored indices -- no thread waits for another,
 //                   vertical before horizontal as T.800 F.4.2 orders it (integer lifting does not commute)
-//   k_jp2k_blocks   one wave per code block: the wave stages the block into LDS as sign/magnitude in stripe-column
-//                   order and finds its top bit-plane, then lane 0 runs the serial coder of jp2k_t1.inc on LDS state
+//   k_jp2k_blocks   one wave per code block: the wave zeroes the flag words, fills the two tables, stages the block into
+//                   LDS as sign/magnitude in stripe-column order and finds its top bit-plane, then lane 0 runs the
+//                   serial coder of jp2k_t1.inc (t1_encode_block: the coding-pass walk the decoder shares) on LDS state
 //                   (19.4 KB per block -- mag 16384 + st 2376 + mqtab 376 + zc 256 + cx 32 + top 4 = 19428 bytes: eight
 //                   blocks per CU) and writes the bytes into the block's slot
 //   k_jp2k_compact  packs the slots back to back behind an exclusive scan of the lengths
@@ -47,13 +48,6 @@ __global__ __launch_bounds__(256) void k_jp2k_shift(const uint16_t* __restrict__
     A[(size_t)slab * g.slab + (size_t)ly * g.tw + lx] = v - (1 << (bits - 1));
 }
 
-__device__ __forceinline__ int jp2k_mirror(int j, int n)
-{
-    if (j < 0) j = -j;
-    if (j > n - 1) j = 2 * (n - 1) - j;
-    return j < 0 ? -j : j;
-}
-
 // level: decompositions already done (the input is the LL region of that level).  VERT: along y.
 template <bool VERT>
 __global__ __launch_bounds__(256) void k_jp2k_lift(const int32_t* __restrict__ src, int32_t* __restrict__ dst, Jp2kDev g, int level)
@@ -71,7 +65,7 @@ __global__ __launch_bounds__(256) void k_jp2k_lift(const int32_t* __restrict__ s
     if (n == 1) out = line[0];
     else {
         const int sn = (n + 1) >> 1;
-        auto X = [&](int j) { return line[(size_t)jp2k_mirror(j, n) * step]; };
+        auto X = [&](int j) { return line[(size_t)jp2k::mirror(j, n) * step]; };
         if (o >= sn) {
             const int p = 2 * (o - sn) + 1;
             out = X(p) - ((X(p - 1) + X(p + 1)) >> 1);
@@ -99,8 +93,8 @@ __global__ __launch_bounds__(64) void k_jp2k_blocks(const int32_t* __restrict__ 
     const int lane = threadIdx.x;
     const int bw = min((int)b.w, 64), bh = min((int)b.h, 64);
     if (lane == 0) top = 0;
-    for (int k = lane; k < jp2k::MQ_ENTRIES; k += 64) mqtab[k] = jp2k::mq_entry(k);
-    for (int k = lane; k < 256; k += 64) zc[k] = (uint8_t)jp2k::zc_lut_entry(k, b.orient);
+    for (int k = lane; k < jp2k::T1_NST * jp2k::T1_STW; k += 64) st[k] = 0;
+    jp2k::t1_fill_tables(mqtab, zc, b.orient, lane, 64);
     __syncthreads();
     const int32_t* src = A + (size_t)b.slab * g.slab + (size_t)b.y * g.tw + b.x;
     uint32_t mx = 0;

@@ -3,8 +3,9 @@
 // transform included -- with the planes left in HBM.  The host parses the file into a validated table of code blocks (jp2k_t2d.inc); tier-1 and the wavelet, which
 // are independent per block and per sample, run here:
 //
-//   k_jp2k_unblocks   one wave per code block: the wave zeroes the block's LDS state, lane 0 runs the serial decoder of
-//                     jp2k_t1d.inc on it, reading the block's bytes from the file's copy in HBM (19.4 KB of LDS per
+//   k_jp2k_unblocks   one wave per code block: the wave zeroes the block's LDS state and fills the two tables, lane 0 runs
+//                     the serial decoder of jp2k_t1d.inc (t1_decode_block: the coding-pass walk the coder shares) on it,
+//                     reading the block's bytes from the file's copy in HBM (19.4 KB of LDS per
 //                     block -- mag 16384 + st 2376 + mqtab 376 + zc 256 + cx 32 = 19424 bytes: eight blocks per CU),
 //                     then the wave stores the block as signed int32 into its tile-component slab (Mallat layout);
 //                     a block the file does not include stores zeros
@@ -70,8 +71,7 @@ __global__ __launch_bounds__(64) void k_jp2k_unblocks(const uint8_t* __restrict_
     const int bw = min((int)b.w, 64), bh = min((int)b.h, 64);
     for (int k = lane; k < 16 * 64 * 4; k += 64) mag[k] = 0;
     for (int k = lane; k < jp2k::T1_NST * jp2k::T1_STW; k += 64) st[k] = 0;
-    for (int k = lane; k < jp2k::MQ_ENTRIES; k += 64) mqtab[k] = jp2k::mq_entry(k);
-    for (int k = lane; k < 256; k += 64) zc[k] = (uint8_t)jp2k::zc_lut_entry(k, b.orient & 3);
+    jp2k::t1_fill_tables(mqtab, zc, b.orient & 3, lane, 64);
     __syncthreads();
     if (lane == 0 && b.passes && b.offset <= file_bytes && b.length <= file_bytes - b.offset)
         jp2k::t1_decode_block(mag, st, cx, mqtab, zc, bw, bh, (int)b.numbps, (int)b.passes, file + b.offset, (int)b.length);
@@ -85,13 +85,6 @@ __global__ __launch_bounds__(64) void k_jp2k_unblocks(const uint8_t* __restrict_
             dst[(size_t)y * g.tw + lane] = (m >> 31) ? -v : v;
         }
     }
-}
-
-__device__ __forceinline__ int jp2kd_mirror(int j, int n)      // n >= 2, -2 <= j <= n + 1
-{
-    if (j < 0) j = -j;
-    if (j > n - 1) j = 2 * (n - 1) - j;
-    return j < 0 ? -j : j;
 }
 
 // level: the decomposition that is undone (0 the finest).  VERT: along y.  The region is the tile-component's
@@ -131,8 +124,8 @@ __global__ __launch_bounds__(256) void k_jp2k_unlift(const int32_t* __restrict__
             const int i = par + k;
             return (i & 1) ? line[(size_t)(nlow + (i >> 1) - (par >> 1)) * step] : lowline[(size_t)((i >> 1) - ((par + 1) >> 1)) * step];
         };
-        auto EVEN = [&](int m) { return IL(m) - ((IL(jp2kd_mirror(m - 1, n)) + IL(jp2kd_mirror(m + 1, n)) + 2) >> 2); };
-        if ((par + o) & 1) out = IL(o) + ((EVEN(jp2kd_mirror(o - 1, n)) + EVEN(jp2kd_mirror(o + 1, n))) >> 1);
+        auto EVEN = [&](int m) { return IL(m) - ((IL(jp2k::mirror(m - 1, n)) + IL(jp2k::mirror(m + 1, n)) + 2) >> 2); };
+        if ((par + o) & 1) out = IL(o) + ((EVEN(jp2k::mirror(o - 1, n)) + EVEN(jp2k::mirror(o + 1, n))) >> 1);
         else out = EVEN(o);
     }
     dst[(size_t)slab * g.slab + (size_t)oy * g.tw + ox] = out;

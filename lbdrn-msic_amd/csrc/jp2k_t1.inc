@@ -1,20 +1,29 @@
 // JPEG 2000 tier-1 (ITU-T T.800 Annex C: the MQ arithmetic coder; Annex D: coefficient bit modelling) for one code block
 // of at most 64 x 64 coefficients, code-block style 0: every magnitude bit-plane from the first non-zero one, three
-// passes per plane (significance propagation, magnitude refinement, clean-up with the run-length mode), 19 contexts,
-// one codeword segment closed by the standard's flush.  Included by jp2k.hip; every function is
-// JP2K_HD (__host__ __device__ under hipcc, nothing elsewhere), so the same text can be compiled by a host compiler and
-// judged by a JPEG 2000 decoder without a GPU.  The library itself calls it from k_jp2k_blocks only.
+// passes per plane (significance propagation, magnitude refinement, clean-up with the run-length mode), 19 contexts, one
+// codeword segment closed by the standard's flush.  Included by jp2k.hip (the coder, called from k_jp2k_blocks only) and,
+// through jp2k_t1d.inc (the MQ decoder and the decoder's policy), by jp2k_dec.hip; every function is JP2K_HD (__host__
+// __device__ under hipcc, nothing elsewhere), so a host compiler builds the same text and CPU tests judge both directions
+// byte for byte against an independent codec without a GPU.
 //
-// State of a block, all of it in memory the caller provides (LDS in the kernel):
-//   mag[stripe][col][4]   sign (bit 31) and magnitude of the four samples of a stripe column: one 128-bit read per column
+// The scan of Annex D exists once: t1_walk owns the plane / pass / stripe / column loops, the register windows, the flag
+// words and every context choice.  t1_encode_block (here) and t1_decode_block (jp2k_t1d.inc) are its only callers; each
+// hands it a policy (T1Coder, T1Decoder) that says where a decision comes from -- a bit of `mag` that is MQ-coded, or an
+// MQ-decoded bit that is entered into `mag` -- and nothing else.
+//
+// State of a block, all of it in memory the CALLER provides (LDS in the kernels).  The caller fills the two tables
+// (t1_fill_tables) and ZEROES `st`, and `mag` too before decoding; the entry points initialise `cx`:
+//   mag[stripe][col][4]   sign (bit 31) and magnitude of the four samples of a stripe column: the coder reads a column it
+//                         visits with one 128-bit read; the decoder enters a sample when it becomes significant and ORs
+//                         its later bits in
 //   st[(stripe+1)*66 + col+1]   16 flag bits of a stripe column: 0-3 significant, 4-7 negative, 8-11 coded in this
 //                               plane's significance pass ("pi"), 12-15 refined before ("mu"); a border of zeros all round
 //   cx[19]                the contexts' states: index into the 94-entry transition table below (2 * state + MPS)
 // and A, C, CT, the pending byte and the position in registers.  A pass walks the stripes column by column with the
 // significance / sign bits of the columns left, here and right in three 6-bit register windows (row -1 comes from the
 // stripe above, row 4 from the one below); a column whose windows are empty is skipped without touching its samples.
-// Every loop is bounded by the geometry: planes <= 31, stripes <= 16, columns <= 64, rows <= 4.  Bytes beyond `cap` are
-// counted, never written.
+// Every loop is bounded by the geometry: planes <= 31, passes <= 91, stripes <= 16, columns <= 64, rows <= 4.  The coder
+// counts bytes beyond `cap` and never writes them; the decoder never reads beyond `len` (MqDec).
 #pragma once
 #include <stdint.h>
 
@@ -78,6 +87,16 @@ JP2K_HD int zc_lut_entry(int idx, int orient)
     const int v = ((idx >> 6) & 1) + ((idx >> 7) & 1);
     const int d = (idx & 1) + ((idx >> 2) & 1) + ((idx >> 3) & 1) + ((idx >> 5) & 1);
     return T1_CTX_ZC + zc_context(h, v, d, orient);
+}
+// mqtab[94] and zc[256] for a block of a subband of orientation `orient`, filled by `nlanes` callers of which this one is
+// `lane` (the wave in the kernels; 0 of 1 on a host).  One loop on purpose: as two loops inlined into the kernels, hipcc
+// 7.2 allocates k_jp2k_blocks and k_jp2k_unblocks 45 vector registers instead of 16 (DESIGN 7).
+JP2K_HD void t1_fill_tables(uint32_t* mqtab, uint8_t* zc, int orient, int lane, int nlanes)
+{
+    for (int k = lane; k < 256; k += nlanes) {
+        if (k < MQ_ENTRIES) mqtab[k] = mq_entry(k);
+        zc[k] = (uint8_t)zc_lut_entry(k, orient);
+    }
 }
 
 struct Mq {
@@ -154,8 +173,8 @@ JP2K_HD int t1_nbr(uint32_t L, uint32_t M, uint32_t R, int r)
 {
     return (int)(((L >> r) & 7u) | (((R >> r) & 7u) << 3) | (((M >> r) & 1u) << 6) | (((M >> (r + 2)) & 1u) << 7));
 }
-// T.800 Table D.3: sign context and the bit the sign is XORed with
-JP2K_HD void t1_sign(Mq& mq, uint32_t L, uint32_t M, uint32_t R, uint32_t Ln, uint32_t Mn, uint32_t Rn, int r, int neg)
+// T.800 Table D.3: the sign context of row r and, in x, the bit the sign is XORed with
+JP2K_HD int t1_sign_ctx(uint32_t L, uint32_t M, uint32_t R, uint32_t Ln, uint32_t Mn, uint32_t Rn, int r, int& x)
 {
     const int lp = (int)((L >> (r + 1)) & 1u), ln = (int)((Ln >> (r + 1)) & 1u);
     const int rp = (int)((R >> (r + 1)) & 1u), rn = (int)((Rn >> (r + 1)) & 1u);
@@ -165,33 +184,36 @@ JP2K_HD void t1_sign(Mq& mq, uint32_t L, uint32_t M, uint32_t R, uint32_t Ln, ui
     const int hpos = (lp & ~ln) | (rp & ~rn), hneg = ln | rn;
     const int vpos = (up & ~un) | (dp & ~dn), vneg = un | dn;
     const int h = hpos - hneg, v = vpos - vneg;
-    const int ctx = h != 0 ? 12 + h * v : (v != 0 ? 10 : 9);
-    const int x = (h < 0 || (h == 0 && v < 0)) ? 1 : 0;
-    mq.encode(neg ^ x, ctx);
+    x = (h < 0 || (h == 0 && v < 0)) ? 1 : 0;
+    return h != 0 ? 12 + h * v : (v != 0 ? 10 : 9);
+}
+// the sample at row r has just become significant in plane p: its sign, and its entry into the column's windows
+template <class Io>
+JP2K_HD void t1_found(Io& io, uint32_t L, uint32_t& M, uint32_t R, uint32_t Ln, uint32_t& Mn, uint32_t Rn, int r, int p)
+{
+    int x;
+    const int ctx = t1_sign_ctx(L, M, R, Ln, Mn, Rn, r, x);
+    const uint32_t neg = io.sign(r, p, ctx, x);
+    M |= 2u << r;
+    Mn |= neg << (r + 1);
 }
 
-struct T1Result { int bytes, passes, numbps; };
-
-// Codes the block.  w, h: its size; numbps: magnitude bits of its largest coefficient (0: nothing is coded);
-// zc: the 256-entry zero-coding table of the block's subband; st and cx are initialised here.
-JP2K_HD T1Result t1_encode_block(const uint32_t* mag, uint16_t* st, uint8_t* cx, const uint32_t* mqtab, const uint8_t* zc,
-                                 int w, int h, int numbps, uint8_t* out, int cap)
+// The coding passes of a w x h block (1..64 each) from bit-plane numbps - 1 (1..31) down, at most `max_passes` of them;
+// returns how many were done.  st must be zero on entry; zc: the 256-entry zero-coding table of the block's subband.
+// What Io supplies, all for the stripe column last named by column(s, c):
+//   bit(r, p, ctx)        bit p of the sample at row r, coded or decoded in context ctx
+//   refine(r, p, ctx)     the same for a sample that is significant already (the decoder enters the bit into `mag`)
+//   sign(r, p, ctx, x)    the sign of the sample at row r that has become significant in plane p (1: negative), coded or
+//                         decoded as sign ^ x in context ctx (the decoder enters the sample into `mag`)
+//   run(p)                the run-length symbol of a column of four: -1 when none of them has bit p, else the first row
+//                         that has (T1_CTX_RL, then the row's two bits in T1_CTX_UNI)
+template <class Io>
+JP2K_HD int t1_walk(Io& io, uint16_t* st, const uint8_t* zc, int w, int h, int numbps, int max_passes)
 {
-    T1Result res = {0, 0, numbps};
-    if (numbps <= 0 || w <= 0 || h <= 0) return res;
-    if (numbps > 31) numbps = 31;
-    for (int k = 0; k < T1_NST * T1_STW; ++k) st[k] = 0;
-    for (int k = 0; k < T1_NCTX; ++k) cx[k] = 0;
-    cx[T1_CTX_ZC] = 2 * 4;
-    cx[T1_CTX_RL] = 2 * 3;
-    cx[T1_CTX_UNI] = 2 * 46;
-    Mq mq;
-    mq.init(out, cap, cx, mqtab);
     const int nstripes = (h + 3) >> 2;
     int passes = 0;
-    for (int p = numbps - 1; p >= 0; --p) {
-        const int first = p == numbps - 1;
-        for (int pass = first ? 2 : 0; pass < 3; ++pass) {
+    for (int p = numbps - 1; p >= 0 && passes < max_passes; --p) {
+        for (int pass = p == numbps - 1 ? 2 : 0; pass < 3 && passes < max_passes; ++pass) {
             for (int s = 0; s < nstripes; ++s) {
                 const int rows = h - 4 * s < 4 ? h - 4 * s : 4;
                 uint16_t* up = st + s * T1_STW + 1;        // st row s is stripe s - 1
@@ -202,28 +224,19 @@ JP2K_HD T1Result t1_encode_block(const uint32_t* mag, uint16_t* st, uint8_t* cx,
                 for (int c = 0; c < w; ++c) {
                     const uint32_t ru = up[c + 1], rc = cur[c + 1], rd = dn[c + 1];
                     const uint32_t R = t1_sig_window(ru, rc, rd), Rn = t1_neg_window(ru, rc, rd);
-                    uint32_t f = cur[c];
+                    const uint32_t f = cur[c];
                     uint32_t pi = (f >> 8) & 15u, mu = (f >> 12) & 15u;
                     const uint32_t any = L | M | R;
-                    const uint32_t* mp = mag + ((size_t)s * 64 + c) * 4;
                     if (pass == 0) {
                         if (any) {
-                            const uint32_t m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
+                            io.column(s, c);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 if (r < rows && !((M >> (r + 1)) & 1u)) {
                                     const int nb = t1_nbr(L, M, R, r);
                                     if (nb) {
-                                        const uint32_t m = r == 0 ? m0 : (r == 1 ? m1 : (r == 2 ? m2 : m3));
-                                        const int bit = (int)((m >> p) & 1u);
-                                        mq.encode(bit, zc[nb]);
                                         pi |= 1u << r;
-                                        if (bit) {
-                                            const int neg = (int)(m >> 31);
-                                            t1_sign(mq, L, M, R, Ln, Mn, Rn, r, neg);
-                                            M |= 2u << r;
-                                            Mn |= (uint32_t)neg << (r + 1);
-                                        }
+                                        if (io.bit(r, p, zc[nb])) t1_found(io, L, M, R, Ln, Mn, Rn, r, p);
                                     }
                                 }
                             }
@@ -232,53 +245,29 @@ JP2K_HD T1Result t1_encode_block(const uint32_t* mag, uint16_t* st, uint8_t* cx,
                     } else if (pass == 1) {
                         const uint32_t todo = ((M >> 1) & 15u) & ~pi;
                         if (todo) {
-                            const uint32_t m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
+                            io.column(s, c);
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
-                                if ((todo >> r) & 1u) {
-                                    const uint32_t m = r == 0 ? m0 : (r == 1 ? m1 : (r == 2 ? m2 : m3));
-                                    const int ctx = ((mu >> r) & 1u) ? 16 : (t1_nbr(L, M, R, r) ? 15 : 14);
-                                    mq.encode((int)((m >> p) & 1u), ctx);
-                                }
+                                if ((todo >> r) & 1u) io.refine(r, p, ((mu >> r) & 1u) ? 16 : (t1_nbr(L, M, R, r) ? 15 : 14));
                             }
                             mu |= todo;
                             cur[c] = (uint16_t)((f & 0x0FFFu) | (mu << 12));
                         }
                     } else {
-                        const uint32_t m0 = mp[0], m1 = mp[1], m2 = mp[2], m3 = mp[3];
-                        int r0 = 0;
-                        bool coded = true;
+                        io.column(s, c);
+                        int r0 = 0;                // the first row that is coded sample by sample; -1: none is
                         if (rows == 4 && !any) {   // run-length mode: four insignificant samples without a significant neighbour
-                            const uint32_t b = ((m0 >> p) & 1u) | (((m1 >> p) & 1u) << 1) | (((m2 >> p) & 1u) << 2) | (((m3 >> p) & 1u) << 3);
-                            if (!b) {
-                                mq.encode(0, T1_CTX_RL);
-                                coded = false;
-                            } else {
-                                mq.encode(1, T1_CTX_RL);
-                                r0 = (b & 1u) ? 0 : ((b & 2u) ? 1 : ((b & 4u) ? 2 : 3));
-                                mq.encode(r0 >> 1, T1_CTX_UNI);
-                                mq.encode(r0 & 1, T1_CTX_UNI);
-                                const uint32_t m = r0 == 0 ? m0 : (r0 == 1 ? m1 : (r0 == 2 ? m2 : m3));
-                                const int neg = (int)(m >> 31);
-                                t1_sign(mq, L, M, R, Ln, Mn, Rn, r0, neg);
-                                M |= 2u << r0;
-                                Mn |= (uint32_t)neg << (r0 + 1);
+                            r0 = io.run(p);
+                            if (r0 >= 0) {
+                                t1_found(io, L, M, R, Ln, Mn, Rn, r0, p);
                                 ++r0;
                             }
                         }
-                        if (coded) {
+                        if (r0 >= 0) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) {
                                 if (r >= r0 && r < rows && !((M >> (r + 1)) & 1u) && !((pi >> r) & 1u)) {
-                                    const uint32_t m = r == 0 ? m0 : (r == 1 ? m1 : (r == 2 ? m2 : m3));
-                                    const int bit = (int)((m >> p) & 1u);
-                                    mq.encode(bit, zc[t1_nbr(L, M, R, r)]);
-                                    if (bit) {
-                                        const int neg = (int)(m >> 31);
-                                        t1_sign(mq, L, M, R, Ln, Mn, Rn, r, neg);
-                                        M |= 2u << r;
-                                        Mn |= (uint32_t)neg << (r + 1);
-                                    }
+                                    if (io.bit(r, p, zc[t1_nbr(L, M, R, r)])) t1_found(io, L, M, R, Ln, Mn, Rn, r, p);
                                 }
                             }
                             cur[c] = (uint16_t)(((M >> 1) & 15u) | (((Mn >> 1) & 15u) << 4) | (mu << 12));   // pi cleared for the next plane
@@ -291,8 +280,74 @@ JP2K_HD T1Result t1_encode_block(const uint32_t* mag, uint16_t* st, uint8_t* cx,
             ++passes;
         }
     }
-    res.bytes = mq.flush();
-    res.passes = passes;
+    return passes;
+}
+
+// What both entry points (t1_encode_block, t1_decode_block) do first.  False: there is nothing to code.  Otherwise the arguments are clamped to what the
+// state holds and the contexts are in their initial states (T.800 Table D.7).
+JP2K_HD bool t1_begin(uint8_t* cx, int& w, int& h, int& numbps)
+{
+    if (numbps <= 0 || w <= 0 || h <= 0) return false;
+    if (numbps > 31) numbps = 31;
+    if (w > 64) w = 64;
+    if (h > 64) h = 64;
+    for (int k = 0; k < T1_NCTX; ++k) cx[k] = 0;
+    cx[T1_CTX_ZC] = 2 * 4;
+    cx[T1_CTX_RL] = 2 * 3;
+    cx[T1_CTX_UNI] = 2 * 46;
+    return true;
+}
+
+struct T1Coder {           // a decision is a bit of `mag`, which is MQ-coded
+    Mq mq;
+    const uint32_t* mag;
+    uint32_t m0, m1, m2, m3;
+
+    JP2K_HD void column(int s, int c)
+    {
+        const uint32_t* mp = mag + ((size_t)s * 64 + c) * 4;
+        m0 = mp[0]; m1 = mp[1]; m2 = mp[2]; m3 = mp[3];
+    }
+    JP2K_HD uint32_t sample(int r) const { return r == 0 ? m0 : (r == 1 ? m1 : (r == 2 ? m2 : m3)); }
+    JP2K_HD int bit(int r, int p, int ctx)
+    {
+        const int d = (int)((sample(r) >> p) & 1u);
+        mq.encode(d, ctx);
+        return d;
+    }
+    JP2K_HD void refine(int r, int p, int ctx) { bit(r, p, ctx); }
+    JP2K_HD uint32_t sign(int r, int, int ctx, int x)
+    {
+        const uint32_t neg = sample(r) >> 31;
+        mq.encode((int)neg ^ x, ctx);
+        return neg;
+    }
+    JP2K_HD int run(int p)
+    {
+        const uint32_t b = ((m0 >> p) & 1u) | (((m1 >> p) & 1u) << 1) | (((m2 >> p) & 1u) << 2) | (((m3 >> p) & 1u) << 3);
+        mq.encode(b != 0, T1_CTX_RL);
+        if (!b) return -1;
+        const int r0 = (b & 1u) ? 0 : ((b & 2u) ? 1 : ((b & 4u) ? 2 : 3));
+        mq.encode(r0 >> 1, T1_CTX_UNI);
+        mq.encode(r0 & 1, T1_CTX_UNI);
+        return r0;
+    }
+};
+
+struct T1Result { int bytes, passes, numbps; };
+
+// Codes the block.  w, h: its size; numbps: magnitude bits of its largest coefficient (0: nothing is coded);
+// zc: the 256-entry zero-coding table of the block's subband; st must be zero on entry.
+JP2K_HD T1Result t1_encode_block(const uint32_t* mag, uint16_t* st, uint8_t* cx, const uint32_t* mqtab, const uint8_t* zc,
+                                 int w, int h, int numbps, uint8_t* out, int cap)
+{
+    T1Result res = {0, 0, numbps};
+    if (!t1_begin(cx, w, h, numbps)) return res;
+    T1Coder io;
+    io.mag = mag;
+    io.mq.init(out, cap, cx, mqtab);
+    res.passes = t1_walk(io, st, zc, w, h, numbps, 3 * numbps - 2);   // every pass there is
+    res.bytes = io.mq.flush();
     return res;
 }
 

@@ -1,22 +1,16 @@
-// JPEG 2000 tier-1 DECODER (ITU-T T.800 Annex C.3: the MQ decoder -- INITDEC, DECODE, BYTEIN, RENORMD; Annex D: the three
-// passes per bit-plane over the 19 contexts, in the scan of D.1) for one code block of at most 64 x 64 coefficients,
-// code-block style 0, one codeword segment.  The counterpart of jp2k_t1.inc, whose MQ table, context tables, flag-word
-// layout and register windows it uses; included by jp2k_dec.hip and called from k_jp2k_unblocks only.  Every function is
-// JP2K_HD, so a host compiler builds the same text and a CPU test judges it against an independent decoder.
-//
-// State of a block, all of it in memory the caller provides (LDS in the kernel) and has ZEROED (mag and st):
-//   mag[stripe][col][4]   receives sign (bit 31) and magnitude of the four samples of a stripe column
-//   st[(stripe+1)*66 + col+1]   the 16 flag bits of a stripe column, as in the coder
-//   cx[19]                the contexts' states (initialised here)
-// The bytes are read from `data[0 .. len)`; beyond them the decoder is fed 0xFF, as C.3.4 has it for the end of the
-// segment (0xFF 0xFF is a marker, which BYTEIN never steps over), so no position beyond `len` is ever read and a
-// truncated or damaged segment decodes to SOME coefficients in bounded time: planes <= 31, passes <= 91, stripes <= 16,
-// columns <= 64, rows <= 4.
+// JPEG 2000 tier-1 DECODER for one code block: the MQ decoder (ITU-T T.800 Annex C.3), the policy that makes t1_walk
+// (jp2k_t1.inc, which owns the scan of Annex D, the tables, the flag words and the state layout) a decoder, and
+// t1_decode_block.  Included by jp2k_dec.hip and called from k_jp2k_unblocks only.  Every function is JP2K_HD, so a host
+// compiler builds the same text and a CPU test judges it against an independent decoder.  The caller provides the state,
+// fills the tables (t1_fill_tables) and ZEROES mag and st.
 #pragma once
 #include "jp2k_t1.inc"
 
 namespace jp2k {
 
+// T.800 C.3: INITDEC, DECODE, BYTEIN, RENORMD.  The bytes are read from in[0 .. len); beyond them the decoder is fed 0xFF,
+// as C.3.4 has it for the end of the segment (0xFF 0xFF is a marker, which BYTEIN never steps over), so no position
+// beyond `len` is ever read and a truncated or damaged segment decodes to SOME coefficients in bounded time.
 struct MqDec {
     uint32_t A, C;
     int CT, pos, len;
@@ -74,20 +68,30 @@ struct MqDec {
     }
 };
 
-// T.800 Table D.3 read backwards: the sign of the sample at row r that has just become significant
-JP2K_HD int t1d_sign(MqDec& mq, uint32_t L, uint32_t M, uint32_t R, uint32_t Ln, uint32_t Mn, uint32_t Rn, int r)
-{
-    const int lp = (int)((L >> (r + 1)) & 1u), ln = (int)((Ln >> (r + 1)) & 1u);
-    const int rp = (int)((R >> (r + 1)) & 1u), rn = (int)((Rn >> (r + 1)) & 1u);
-    const int up = (int)((M >> r) & 1u), un = (int)((Mn >> r) & 1u);
-    const int dp = (int)((M >> (r + 2)) & 1u), dn = (int)((Mn >> (r + 2)) & 1u);
-    const int hpos = (lp & ~ln) | (rp & ~rn), hneg = ln | rn;
-    const int vpos = (up & ~un) | (dp & ~dn), vneg = un | dn;
-    const int h = hpos - hneg, v = vpos - vneg;
-    const int ctx = h != 0 ? 12 + h * v : (v != 0 ? 10 : 9);
-    const int x = (h < 0 || (h == 0 && v < 0)) ? 1 : 0;
-    return mq.decode(ctx) ^ x;
-}
+struct T1Decoder {         // a decision is MQ-decoded and entered into `mag`
+    MqDec mq;
+    uint32_t* mag;
+    uint32_t* mp;
+
+    JP2K_HD void column(int s, int c) { mp = mag + ((size_t)s * 64 + c) * 4; }
+    JP2K_HD int bit(int, int, int ctx) { return mq.decode(ctx); }
+    JP2K_HD void refine(int r, int p, int ctx)
+    {
+        if (mq.decode(ctx)) mp[r] |= 1u << p;
+    }
+    JP2K_HD uint32_t sign(int r, int p, int ctx, int x)
+    {
+        const uint32_t neg = (uint32_t)(mq.decode(ctx) ^ x);
+        mp[r] = (1u << p) | (neg << 31);
+        return neg;
+    }
+    JP2K_HD int run(int)
+    {
+        if (!mq.decode(T1_CTX_RL)) return -1;
+        const int hi = mq.decode(T1_CTX_UNI);
+        return hi << 1 | mq.decode(T1_CTX_UNI);
+    }
+};
 
 // Decodes the first `passes` coding passes of a block whose first coded bit-plane is numbps - 1 (passes beyond
 // 3 * numbps - 2 do not exist and are not run).  w, h: the block's size; zc: the 256-entry zero-coding table of its
@@ -95,105 +99,11 @@ JP2K_HD int t1d_sign(MqDec& mq, uint32_t L, uint32_t M, uint32_t R, uint32_t Ln,
 JP2K_HD void t1_decode_block(uint32_t* mag, uint16_t* st, uint8_t* cx, const uint32_t* mqtab, const uint8_t* zc, int w, int h,
                              int numbps, int passes, const uint8_t* data, int len)
 {
-    if (numbps <= 0 || passes <= 0 || w <= 0 || h <= 0) return;
-    if (numbps > 31) numbps = 31;
-    if (w > 64) w = 64;
-    if (h > 64) h = 64;
-    for (int k = 0; k < T1_NCTX; ++k) cx[k] = 0;
-    cx[T1_CTX_ZC] = 2 * 4;
-    cx[T1_CTX_RL] = 2 * 3;
-    cx[T1_CTX_UNI] = 2 * 46;
-    MqDec mq;
-    mq.init(data, len, cx, mqtab);
-    const int nstripes = (h + 3) >> 2;
-    int done = 0;
-    for (int p = numbps - 1; p >= 0 && done < passes; --p) {
-        const int first = p == numbps - 1;
-        const uint32_t one = 1u << p;
-        for (int pass = first ? 2 : 0; pass < 3 && done < passes; ++pass) {
-            for (int s = 0; s < nstripes; ++s) {
-                const int rows = h - 4 * s < 4 ? h - 4 * s : 4;
-                uint16_t* up = st + s * T1_STW + 1;        // st row s is stripe s - 1
-                uint16_t* cur = up + T1_STW;
-                uint16_t* dn = cur + T1_STW;
-                uint32_t L = 0, Ln = 0;
-                uint32_t M = t1_sig_window(up[0], cur[0], dn[0]), Mn = t1_neg_window(up[0], cur[0], dn[0]);
-                for (int c = 0; c < w; ++c) {
-                    const uint32_t ru = up[c + 1], rc = cur[c + 1], rd = dn[c + 1];
-                    const uint32_t R = t1_sig_window(ru, rc, rd), Rn = t1_neg_window(ru, rc, rd);
-                    const uint32_t f = cur[c];
-                    uint32_t pi = (f >> 8) & 15u, mu = (f >> 12) & 15u;
-                    const uint32_t any = L | M | R;
-                    uint32_t* mp = mag + ((size_t)s * 64 + c) * 4;
-                    if (pass == 0) {
-                        if (any) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                if (r < rows && !((M >> (r + 1)) & 1u)) {
-                                    const int nb = t1_nbr(L, M, R, r);
-                                    if (nb) {
-                                        pi |= 1u << r;
-                                        if (mq.decode(zc[nb])) {
-                                            const uint32_t neg = (uint32_t)t1d_sign(mq, L, M, R, Ln, Mn, Rn, r);
-                                            M |= 2u << r;
-                                            Mn |= neg << (r + 1);
-                                            mp[r] = one | (neg << 31);
-                                        }
-                                    }
-                                }
-                            }
-                            cur[c] = (uint16_t)(((M >> 1) & 15u) | (((Mn >> 1) & 15u) << 4) | (pi << 8) | (mu << 12));
-                        }
-                    } else if (pass == 1) {
-                        const uint32_t todo = ((M >> 1) & 15u) & ~pi;
-                        if (todo) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                if ((todo >> r) & 1u) {
-                                    const int ctx = ((mu >> r) & 1u) ? 16 : (t1_nbr(L, M, R, r) ? 15 : 14);
-                                    if (mq.decode(ctx)) mp[r] |= one;
-                                }
-                            }
-                            mu |= todo;
-                            cur[c] = (uint16_t)((f & 0x0FFFu) | (mu << 12));
-                        }
-                    } else {
-                        int r0 = 0;
-                        bool coded = true;
-                        if (rows == 4 && !any) {   // run-length mode
-                            if (!mq.decode(T1_CTX_RL)) coded = false;
-                            else {
-                                r0 = mq.decode(T1_CTX_UNI) << 1;
-                                r0 |= mq.decode(T1_CTX_UNI);
-                                const uint32_t neg = (uint32_t)t1d_sign(mq, L, M, R, Ln, Mn, Rn, r0);
-                                M |= 2u << r0;
-                                Mn |= neg << (r0 + 1);
-                                mp[r0] = one | (neg << 31);
-                                ++r0;
-                            }
-                        }
-                        if (coded) {
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                if (r >= r0 && r < rows && !((M >> (r + 1)) & 1u) && !((pi >> r) & 1u)) {
-                                    if (mq.decode(zc[t1_nbr(L, M, R, r)])) {
-                                        const uint32_t neg = (uint32_t)t1d_sign(mq, L, M, R, Ln, Mn, Rn, r);
-                                        M |= 2u << r;
-                                        Mn |= neg << (r + 1);
-                                        mp[r] = one | (neg << 31);
-                                    }
-                                }
-                            }
-                            cur[c] = (uint16_t)(((M >> 1) & 15u) | (((Mn >> 1) & 15u) << 4) | (mu << 12));   // pi cleared for the next plane
-                        }
-                    }
-                    L = M; Ln = Mn;
-                    M = R; Mn = Rn;
-                }
-            }
-            ++done;
-        }
-    }
+    if (passes <= 0 || !t1_begin(cx, w, h, numbps)) return;
+    T1Decoder io;
+    io.mag = io.mp = mag;
+    io.mq.init(data, len, cx, mqtab);
+    t1_walk(io, st, zc, w, h, numbps, passes);
 }
 
 }  // namespace jp2k

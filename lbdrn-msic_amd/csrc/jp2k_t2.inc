@@ -18,6 +18,13 @@ constexpr int TILE = 1024, CBLK = 64, GUARD = 2, MAX_RES = 6;
 constexpr int MAX_SIDE = 32768;   // beyond it a resolution has more than one default precinct
 
 constexpr int ceil_shift(int a, int k) { return (int)(((int64_t)a + (1 << k) - 1) >> k); }
+// whole-sample symmetric extension of a line of n >= 2 samples: the sample that index j in -2 .. n + 1 stands for
+constexpr int mirror(int j, int n)
+{
+    if (j < 0) j = -j;
+    if (j > n - 1) j = 2 * (n - 1) - j;
+    return j < 0 ? -j : j;
+}
 
 struct Band {
     int orient;        // 0 LL, 1 HL, 2 LH, 3 HH

@@ -419,7 +419,6 @@ struct TagTreeReader {  // B.10.2, reading: a node's value is learnt once, as ze
     }
 };
 
-inline int dec_ilog2(uint32_t v) { int n = 0; while (v > 1) { v >>= 1; ++n; } return n; }
 
 inline int dec_get_passes(BitReader& br)   // Table B.4
 {
@@ -461,7 +460,7 @@ inline int64_t dec_packet_header(const uint8_t* in, size_t n, int nbands, const 
             const int passes = dec_get_passes(br);
             int lblock = 3;
             while (br.get() && !br.bad) ++lblock;
-            const int nbits = lblock + dec_ilog2((uint32_t)passes);
+            const int nbits = lblock + floor_log2((uint32_t)passes);
             if (nbits > 31) return -1;
             r[0] = passes;
             r[1] = mb[k] - z;

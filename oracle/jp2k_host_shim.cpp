@@ -3,7 +3,7 @@
 // oracle/jp2k_oracle.c without a GPU.  TEST INFRASTRUCTURE; built by oracle/build.py into oracle/_build/.
 //
 // The only product text restated here is the staging of a block in k_jp2k_blocks (csrc/jp2k.hip): sign / magnitude,
-// mag[((y >> 2) * 64 + x) * 4 + (y & 3)], numbps from the OR of the magnitudes, and the two tables the kernel fills.
+// mag[((y >> 2) * 64 + x) * 4 + (y & 3)], numbps from the OR of the magnitudes, the zeroed flag words and the filled tables.
 #include <stdint.h>
 #include <string.h>
 
@@ -24,8 +24,8 @@ int jp2k_shim_code_block(const int32_t* coef, int stride, int w, int h, int orie
     uint32_t mqtab[jp2k::MQ_ENTRIES];
     uint8_t zc[256], cx[32];
     if (w < 1 || h < 1 || w > 64 || h > 64) return -1;
-    for (int k = 0; k < jp2k::MQ_ENTRIES; ++k) mqtab[k] = jp2k::mq_entry(k);
-    for (int k = 0; k < 256; ++k) zc[k] = (uint8_t)jp2k::zc_lut_entry(k, orient);
+    memset(st, 0, sizeof st);
+    jp2k::t1_fill_tables(mqtab, zc, orient, 0, 1);
     uint32_t top = 0;
     for (int y = 0; y < 64; ++y)
         for (int x = 0; x < 64; ++x) {

@@ -24,8 +24,7 @@ int jp2kd_shim_t1_decode(const uint8_t* data, int len, int w, int h, int orient,
     if (w < 1 || h < 1 || w > 64 || h > 64 || orient < 0 || orient > 3 || len < 0) return -1;
     memset(mag, 0, sizeof mag);
     memset(st, 0, sizeof st);
-    for (int k = 0; k < jp2k::MQ_ENTRIES; ++k) mqtab[k] = jp2k::mq_entry(k);
-    for (int k = 0; k < 256; ++k) zc[k] = (uint8_t)jp2k::zc_lut_entry(k, orient);
+    jp2k::t1_fill_tables(mqtab, zc, orient, 0, 1);
     jp2k::t1_decode_block(mag, st, cx, mqtab, zc, w, h, numbps, passes, data, len);
     for (int y = 0; y < h; ++y)
         for (int x = 0; x < w; ++x) {
