@@ -20,6 +20,9 @@
 //   4. every position chases its chain, independently.
 // List order is irrelevant (each hop takes the maximum step below a bound), so the order in which the atomics
 // land does not affect the result.  tests/test_gpu_randperm.py checks equality with torch.randperm for many (seed, n).
+// tests/test_randperm_reference.py reads the constants below out of this text and proves on the CPU, by a census of the
+// targets, that the (seed, n) pairs and sizes of test_gpu_randperm.py reach every list-length branch of k_links and
+// k_part_links and every size at which the pipeline changes path: change a constant and that test says which edge moved.
 #include <cstdlib>
 #include <cstring>
 

@@ -1,9 +1,18 @@
-"""lbdrn_randperm == torch.randperm of a seeded CPU generator, bit for bit."""
+"""lbdrn_randperm == torch.randperm of a seeded CPU generator, bit for bit.
+
+The second half of the file runs inputs that tests/test_randperm_reference.py has chosen and proven on the CPU: (seed, n)
+pairs whose census reaches every list-length branch of k_links and k_part_links, the sizes at which the pipeline switches
+path or a launch gets a ragged last workgroup (every one derived from the constants parsed out of csrc/randperm.hip),
+and the plans of sampler.DevicePermutationStream against a real DataLoader."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 from lbdrn_hip import ops, sampler
+from test_randperm_reference import (ATOMIC_PAIRS, BATCH_COUNTS, EDGE_SEEDS, FIRST_PART_N, PART_PAIRS, PLAN_SEED, PLANS,  # noqa: E402
+                                     all_part_pairs, edge_sizes, loader_run, torch_randperm)
 
 pytestmark = pytest.mark.gpu
 
@@ -76,3 +85,97 @@ def test_device_stream_replays_dataloader_order(dev):
     st = sampler.DevicePermutationStream(n, epochs, 1, dev)
     for e in range(1, epochs + 1):
         assert torch.equal(st.get(e).cpu(), want[e - 1])
+
+
+# ---- inputs chosen by the CPU census (tests/test_randperm_reference.py::test_pairs_reach_their_branches) ----
+
+@functools.lru_cache(maxsize=None)
+def _want_small(seed, n):
+    """torch's permutation, computed once for the cases that share an n (the small ones only: 0.5 MB each)"""
+    assert n <= 1 << 17
+    return torch_randperm(seed, n)
+
+
+@pytest.mark.parametrize("seed,n", all_part_pairs())
+def test_partitioned_list_branches_one_permutation_per_call(dev, seed, n):
+    """k_part_links orders a position's list in registers (up to LINK_REG entries), in its LDS strip (up to LINK_LDS) or
+    by re-walking the links (longer).  Every "rewalk" pair has all three kinds of list in one permutation, the long one
+    in a partition before the last one ("inner") or in the last one -- of one position at n = 32769, full at 17 * 2048;
+    every "lds" pair stops at the strip."""
+    assert torch.equal(_want_small(seed, n), ops.randperm(seed, n, dev).cpu()), (seed, n)
+
+
+@pytest.mark.parametrize("n", list(PART_PAIRS))
+def test_partitioned_list_branches_share_a_launch(dev, n):
+    """All pairs of one n through one library call: the permutations go through every launch together (blockIdx.y), a
+    permutation whose longest list fits the LDS strip beside ones that re-walk."""
+    seeds = [seed for seed, _, _ in PART_PAIRS[n]]
+    got = ops.randperm(seeds, n, dev).cpu()
+    for c, seed in enumerate(seeds):
+        assert torch.equal(_want_small(seed, n), got[c]), (seed, n)
+    got = ops.randperm(seeds[::-1], n, dev).cpu()   # and in the other order: another permutation first in the workspace
+    for c, seed in enumerate(seeds[::-1]):
+        assert torch.equal(_want_small(seed, n), got[c]), (seed, n)
+
+
+@pytest.mark.parametrize("seed,n", ATOMIC_PAIRS)
+def test_atomic_path_lists_longer_than_the_registers(dev, seed, n):
+    """k_links (n <= 32768 and n > 2048^2) re-walks a list of more than LINK_REG entries: the common case at any n
+    beyond a few thousand, pinned here by the census below and above the partitioned sizes."""
+    assert torch.equal(torch_randperm(seed, n), ops.randperm(seed, n, dev).cpu()), (seed, n)
+
+
+# ---- size edges of the partitioned path (tests/test_randperm_reference.py::test_edge_sizes_are_the_edges_they_are_named_after) ----
+
+@pytest.mark.parametrize("what,n", list(edge_sizes().items()), ids=[str(n) for n in edge_sizes().values()])
+def test_size_edges_equal_torch_randperm(dev, what, n):
+    """The sizes at which lbdrn_randperm changes path (16 * PART_SIZE, PART_MAX_N), a last partition or a last counting
+    workgroup holds one entry, and the row of partition totals needs a second turn of k_part_scan_rows' loop -- of one
+    entry, and ragged.  Three seeds in one call, and the first of them alone."""
+    seeds = list(EDGE_SEEDS)
+    want = [torch_randperm(seed, n) for seed in seeds]
+    got = ops.randperm(seeds, n, dev).cpu()
+    for c, seed in enumerate(seeds):
+        assert torch.equal(want[c], got[c]), (what, seed, n)
+    assert torch.equal(want[0], ops.randperm(seeds[0], n, dev).cpu()), (what, seeds[0], n)
+
+
+@pytest.mark.parametrize("count", BATCH_COUNTS)
+def test_batch_counts_at_the_first_partitioned_size(dev, count):
+    """ops.randperm hands the library at most 32 seeds per call: one seed, one short of a full call, a full call, and a
+    full call followed by a call of one.  Every row against torch; no row may repeat its neighbour's permutation."""
+    n = FIRST_PART_N
+    seeds = [2 ** 40 + 17, 2508, 1] + list(range(7000, 7030))   # (2508: a list that re-walks; 1: none beyond the LDS strip)
+    seeds = seeds[:count]
+    assert len(seeds) == count == len(set(s & 0xFFFFFFFF for s in seeds))
+    got = ops.randperm(seeds, n, dev)
+    assert got.shape == (count, n)
+    got = got.cpu()
+    for c, seed in enumerate(seeds):
+        assert torch.equal(_want_small(seed, n), got[c]), (count, c, seed)
+    for c in range(count - 1):
+        assert not torch.equal(got[c], got[c + 1]), (count, c)
+
+
+# ---- DevicePermutationStream (tests/test_randperm_reference.py::test_plan_and_seed_draws_replay_the_loader) ----
+
+@pytest.mark.parametrize("handed_in", [False, True], ids=["seeds-drawn-inside", "train-seeds-handed-in"])
+@pytest.mark.parametrize("epochs,val,n,bs,evals", PLANS)
+def test_device_stream_replays_the_loader_for_every_plan(dev, epochs, val, n, bs, evals, handed_in):
+    """A real DataLoader(shuffle=True), iterated once per training epoch and once per evaluation: the stream hands out
+    the loader's order for every epoch and leaves the global generator where the loader's run left it -- with the seeds
+    drawn by the stream, and with train_seeds drawn beforehand (codec.draw_fit's way), when the stream draws nothing."""
+    orders, after = loader_run(epochs, n, bs, tuple(evals))
+    torch.manual_seed(PLAN_SEED)
+    if handed_in:
+        seeds = sampler.draw_pass_seeds(sampler.epoch_plan(epochs, val))
+        st = sampler.DevicePermutationStream(n, epochs, val, dev, train_seeds=seeds)
+    else:
+        st = sampler.DevicePermutationStream(n, epochs, val, dev)
+    assert int(torch.empty((), dtype=torch.int64).random_().item()) == after
+    assert [hi - lo for lo, hi, _, _ in st._batches] == ([1] if epochs == 1 else [1, epochs - 1])
+    for e in list(range(epochs, 0, -1)) + list(range(1, epochs + 1)):   # (any order, any number of times)
+        assert torch.equal(st.get(e).cpu(), orders[e - 1]), e
+    with pytest.raises(KeyError):
+        st.get(epochs + 1)
+    st.close()
