@@ -1,4 +1,4 @@
-"""Build liblbdrn_hip.so and liblbdrn_jp2k_dec.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so and liblbdrn_resid.so for gfx950 with hipcc (in-tree, next to the Python host code).
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -68,6 +68,29 @@ def build_jp2k_dec(force=False):
     return JP2K_DEC_OUT
 
 
+RESID_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_resid.so")
+RESID_SRCS = ["resid.hip"]
+RESID_DEPS = ["resid.inc", "common.hpp", "exports_resid.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_resid.h"]
+
+
+def build_resid(force=False):
+    """liblbdrn_resid.so (include/lbdrn_resid.h): the residual layer's coder and decoder, a library of its own like
+    liblbdrn_jp2k_dec.so -- same compiler, same flags, its own object file and version script."""
+    if not force and os.path.exists(RESID_OUT):
+        t = os.path.getmtime(RESID_OUT)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in RESID_SRCS + RESID_DEPS + ["build.py"]):
+            return RESID_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = []
+    for src in RESID_SRCS:
+        obj = os.path.join(HERE, src.replace(".hip", ".o"))
+        objs.append(obj)
+        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
+                           "-Wl,--version-script=" + os.path.join(HERE, "exports_resid.map"), "-o", RESID_OUT] + objs)
+    return RESID_OUT
+
+
 def stale():
     if not os.path.exists(OUT):
         return True
@@ -79,6 +102,7 @@ def build(force=False, extra=(), out=None):
     out = out or OUT
     if out == OUT:
         build_jp2k_dec(force)
+        build_resid(force)
     if out == OUT and not force and not stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -110,4 +134,5 @@ if __name__ == "__main__":
     else:
         print(build(force="--force" in sys.argv))
         print(JP2K_DEC_OUT)
+        print(RESID_OUT)
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

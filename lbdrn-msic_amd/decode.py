@@ -7,7 +7,11 @@ bitstream are decoded round-robin on N GPUs and merged on rank 0 (tiles are inde
 while decoding).
 
 `--window X0 Y0 W H` reconstructs that part of the scene only (lbdrn_hip.codec.decode_window): tiles the window does not
-touch are skipped by the byte sizes in the header, touched ones are decoded on a crop with a margin of D."""
+touch are skipped by the byte sizes in the header, touched ones are decoded on a crop with a margin of D.
+
+A file written with `encode.py --max-error T` carries a residual layer behind its payloads: it is applied by default (to a
+window through the layer's rectangle argument: only the blocks the window touches are decoded); `--no-enhancement` gives the
+base reconstruction."""
 import argparse
 import os
 import random
@@ -31,9 +35,9 @@ def read_image_header(bitstream):
     return container.unpack_header(bitstream)
 
 
-def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True):
+def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=None):
     """Decode one image or tile from the front of `bitstream`; returns the remaining bytes
-    (ref decode.py:56-141)."""
+    (ref decode.py:56-141).  layer: the tile's residual body (LBR1), applied to the reconstruction in HBM."""
     nn_payload, bitstream = bitstream[:nn_bytes], bitstream[nn_bytes:]
     base_payload, bitstream = bitstream[:base_bytes], bitstream[base_bytes:]
     base = container.decode_base(base_payload, device=DEVICE, keep_on_device=True)   # ref decode.py:69-73
@@ -44,7 +48,11 @@ def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True):
     # anything is sized by it (ref decode.py:114-120 slices the vector by state_dict shapes)
     need = ops.param_count(ops.make_net(cfg.feature_dim(int(base.shape[0]), D), bc, int(base.shape[0]), nl))
     params = container.decode_weights(nn_payload, expected=need)
-    image = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE)
+    if layer is None:
+        image = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE)
+    else:
+        rec = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE, keep_on_device=True)
+        image = ops.from_device_u16(codec.residual_apply(layer, rec.contiguous()))
     recon_path = f"{dirname}/{filename}_recon.tif"
     test.last_image = image
     if write:
@@ -70,7 +78,12 @@ def decode_window_main(args, rank, world):
     x0, y0, w, h = codec.check_window(args.window, width, height)
     logger.log.info(f"Window: x0={x0} y0={y0} w={w} h={h} of {width} x {height}")
     # the touched tiles are dealt over the ranks like all tiles of a whole decode
-    _, parts = codec.decode_window_pieces(bitstream, args.window, device=DEVICE, take=lambda k, piece: k % world == rank)
+    layer = None if args.no_enhancement else container.unpack_residual_trailer(bitstream)      # (here for tau and the records only)
+    if layer is not None:
+        logger.log.info(f"Residual layer: max error {layer[0]}")
+    # decode_window_pieces applies a layer by default; only --no-enhancement has anything to say to it
+    more = {"enhance": False} if args.no_enhancement else {}
+    _, parts = codec.decode_window_pieces(bitstream, args.window, device=DEVICE, take=lambda k, piece: k % world == rank, **more)
     parts = [(pc.ox, pc.oy, ops.from_device_u16(rec)) for pc, rec in parts]
     gathered = shard.gather_to_root(parts) if world > 1 else [parts]
     if rank == 0:
@@ -89,6 +102,8 @@ def decode_window_main(args, rank, world):
             mse_value = np.mean((org_img.astype(np.float32) - image.astype(np.float32)) ** 2)
             logger.log.info(f"MSE: {mse_value}")
             logger.log.info(f"PSNR: {10 * np.log10(10000 ** 2 / mse_value)}")    # (no bpsp: a property of the whole file)
+            if layer is not None:      # (a file without a layer logs what it always logged)
+                logger.log.info(f"Max error: {int(np.abs(org_img.astype(np.int64) - image.astype(np.int64)).max())}")
     if world > 1:
         shard.finish()
     return 0
@@ -104,6 +119,8 @@ def main(argv=None, shard_tiles=None):
                    help="reconstruct this part of the scene only (scene pixels)")
     p.add_argument("-o", "--out_path", type=str, default=None,
                    help="with --window: where the raster goes (default <name>_recon_x{X0}_y{Y0}_w{W}_h{H}.tif)")
+    p.add_argument("--no-enhancement", dest="no_enhancement", action="store_true",
+                   help="ignore the residual layer of a file that has one: the base reconstruction")
     args = p.parse_args(argv)
     if args.out_path is not None and args.window is None:
         p.error("-o names the raster of a --window decode")
@@ -145,13 +162,17 @@ def main(argv=None, shard_tiles=None):
     ACTIVATION = container.header_activation(bitstream)
     if ACTIVATION is not None and ACTIVATION != FeatCfg.from_constants().activation:
         logger.log.info(f"hidden activation {ACTIVATION} (from the header; constants.HIDDEN_ACTIVATION says otherwise)")
+    layer = None if args.no_enhancement else container.unpack_residual_trailer(bitstream)
+    if layer is not None:
+        logger.log.info(f"Residual layer: max error {layer[0]}")
+    bodies = layer[1] if layer is not None else [None] * (split_ratio * split_ratio)
     bitstream = bitstream[n_hdr:]
     recon_path = f"{dirname}/{basename[:-4]}_recon.tif"
     if split_ratio > 1:
         decoded, offset = [], 0
         for t, (i, j, x0, y0, w, h) in enumerate(tile_windows(width, height, split_ratio)):
             if t % world == rank:
-                test(bitstream[offset:], dirname, f"tile_{i}_{j}", nn_list[t], base_list[t], write=False)
+                test(bitstream[offset:], dirname, f"tile_{i}_{j}", nn_list[t], base_list[t], write=False, layer=bodies[t])
                 decoded.append((t, test.last_image))
             offset += nn_list[t] + base_list[t]
         gathered = shard.gather_to_root(decoded) if world > 1 else [decoded]
@@ -164,7 +185,7 @@ def main(argv=None, shard_tiles=None):
                 merged[:, y0:y0 + h, x0:x0 + w] = tiles[t]
             write_tiff_with_gdal(recon_path, merged)
     elif rank == 0:
-        test(bitstream, dirname, filename, nn_list[0], base_list[0])
+        test(bitstream, dirname, filename, nn_list[0], base_list[0], layer=bodies[0])
     if rank == 0:
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
         if args.org_path is not None:
@@ -175,6 +196,8 @@ def main(argv=None, shard_tiles=None):
             logger.log.info(f"MSE: {mse_value}")
             psnr = 10 * np.log10(10000 ** 2 / mse_value)    # peak fixed at 10000 (ref decode.py:218)
             logger.log.info(f"PSNR: {psnr}")
+            if layer is not None:      # (a file without a layer logs what it always logged)
+                logger.log.info(f"Max error: {int(np.abs(org_img.astype(np.int64) - rec_img.astype(np.int64)).max())}")
             logger.log.info(f"Total size: {nbytes} bytes, bpsp={nbytes * 8 / np.prod(org_img.shape)}")
             os.remove(recon_path)                             # ref decode.py:223-224
     if world > 1:

@@ -3,6 +3,7 @@ and log records as the reference's encode.py (ref encode.py:167-289); the per-im
 fused HIP kernels (lbdrn_hip.codec.fit_image) instead of DataLoader + ignite + autograd.
 
 Bitstream: header | for each tile (row-major): network payload | MSB payload   (ref encode.py:29-36)
+           [| residual-layer trailer, with --max-error T: container.pack_residual_trailer]
 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N encode.py ... -sr S` fits the S*S tiles of the
 image round-robin on N GPUs (one process per GPU, no exchange during the fits) and rank 0 assembles the
@@ -124,6 +125,16 @@ def report_and_pack(args, res, base_ahead=None):
     return nn_payload, base_payload
 
 
+def residual_layer(args, res, tile, nn_payload):
+    """--max-error T: the tile's residual layer, coded in a closed loop against what the decoder will reconstruct from
+    `nn_payload` and verified before it is handed back (lbdrn_hip.codec.residual_encode) -> LBR1 body."""
+    body, err = codec.residual_encode(res, args.max_error, tile, nn_payload, args.K, args.D, args.base_channel, args.num_layers,
+                                      cfg=FeatCfg.from_constants(), device=DEVICE)
+    logger.log.info(f"Max error: {err}")
+    logger.log.info(f"Residual layer: {len(body)} bytes: bpsp={len(body) * 8 / res.n_subpixels}")
+    return body
+
+
 def train_tiles(args, tiles, draws):
     """Several tiles of one image: fitted with IN_FLIGHT of them progressing at a time (their random draws
     were made beforehand, in tile order), then reported one after another like train() would.
@@ -158,6 +169,9 @@ def build_parser():
     p.add_argument("-e", "--epochs", type=int, default=10, help="number of epochs to train (default: 10)")
     p.add_argument("-vd", "--val_duration", type=int, default=1,
                    help="number of epoch duration for val (default: 1)")
+    p.add_argument("--max-error", dest="max_error", type=int, default=None, metavar="T",
+                   help="append a residual layer that bounds |original - reconstruction| by T on every sample (0: lossless); "
+                        "default: no layer")
     return p
 
 
@@ -172,6 +186,8 @@ def main(argv=None, shard_tiles=None):
             container.check_weight_precision(args.precision)
         except ValueError as e:
             parser.error(str(e))
+    if args.max_error is not None and not 0 <= args.max_error <= 65535:
+        parser.error(f"--max-error {args.max_error}: 0 (lossless) .. 65535")
     try:   # likewise an MSB payload codec nobody knows (LBDRN_BASE_CODEC)
         container.check_base_codec(BASE_CODEC)
     except ValueError as e:
@@ -234,24 +250,26 @@ def main(argv=None, shard_tiles=None):
     if jobs and BASE_CODEC.lower() in ("jp2", "jpeg2000", "jp2openjpeg") and os.environ.get("LBDRN_JP2_AHEAD", "1") != "0":
         ahead = BasePayloadsAhead([tile for _, tile in jobs], args.K)
     results = train_tiles(args, jobs, [draws[t] for t in mine]) if jobs else []
-    fitted = []   # (tile index, nn payload, MSB payload, captured log records or None)
-    for k, (t, (path, _), res) in enumerate(zip(mine, jobs, results)):
+    fitted = []   # (tile index, nn payload, MSB payload, captured log records or None, residual body or None)
+    for k, (t, (path, tile), res) in enumerate(zip(mine, jobs, results)):
         args.path = path
         take = (lambda k=k: ahead.take(k)) if ahead is not None else None
         if world > 1:
             with logger.capture() as lines:
                 logger.log.info(args)
                 nn, base = report_and_pack(args, res, take)
+                layer = residual_layer(args, res, tile, nn) if args.max_error is not None else None
         else:
             lines = None
             logger.log.info(args)
             nn, base = report_and_pack(args, res, take)
-        fitted.append((t, nn, base, lines))
+            layer = residual_layer(args, res, tile, nn) if args.max_error is not None else None
+        fitted.append((t, nn, base, lines, layer))
     gathered = shard.gather_to_root(fitted) if world > 1 else [fitted]
     if rank == 0:
         tiles = sorted((rec for part in gathered for rec in part), key=lambda rec: rec[0])
         assert [rec[0] for rec in tiles] == list(range(len(windows)))
-        for _, _, _, lines in tiles:
+        for _, _, _, lines, _ in tiles:
             if lines is not None:
                 logger.replay(lines)
         header = container.pack_header(args.split_ratio, width, height, args.K, args.base_channel,
@@ -259,9 +277,11 @@ def main(argv=None, shard_tiles=None):
                                        [len(rec[2]) for rec in tiles], activation=FeatCfg.from_constants().activation)
         with open(bitstream_path, "wb") as f:
             f.write(header)
-            for _, nn, base, _ in tiles:
+            for _, nn, base, _, _ in tiles:
                 f.write(nn)
                 f.write(base)
+            if args.max_error is not None:      # behind everything the header lists: older readers stop before it
+                f.write(container.pack_residual_trailer(args.max_error, [rec[4] for rec in tiles]))
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
     if world > 1:
         shard.finish()

@@ -660,7 +660,7 @@ def fit_images(imgs, K, D, base_channel, num_layers, lr, batch_size, epochs, val
 
 
 def apply_image(base, params, K, D, base_channel, num_layers, cfg=None, device="cuda:0",
-                path=ops.PATH_AUTO, want_y=False):
+                path=ops.PATH_AUTO, want_y=False, keep_on_device=False):
     """Reconstruct one image (or tile) from its MSB plane and fitted weights (ref decode.py:73-134).
     base: numpy [C,H,W] (uint8 or uint16), or the plane already in HBM (int16-storage tensor);
     params: float32 vector in state_dict order."""
@@ -683,9 +683,50 @@ def apply_image(base, params, K, D, base_channel, num_layers, cfg=None, device="
     if p.numel() != ops.param_count(net):
         raise ValueError(f"weight payload has {p.numel()} values, the network needs {ops.param_count(net)}")
     out = ops.decode_fused(geom, net, msb_d, p, want_y=want_y, path=path)
+    if keep_on_device:      # (decode.py applies the residual layer to it where it lies)
+        return out
     if want_y:
         return ops.from_device_u16(out[0]), out[1].cpu().numpy()
     return ops.from_device_u16(out)
+
+
+# ---------------------------------------------------------------- the residual layer (encode.py --max-error)
+
+def residual_encode(fit_result, tau, img, nn_payload, K, D, base_channel, num_layers, cfg=None, device="cuda:0",
+                    path=ops.PATH_AUTO):
+    """The residual layer of one fitted tile -> (LBR1 body, max |orig - recon'| as verified).
+
+    Closed loop: `recon` is what every decoder of this package will compute -- lbdrn_decode_fused on the MSB planes the fit
+    left in HBM with the weights AFTER their payload round trip (container.decode_weights of `nn_payload`, the bytes that go
+    into the file; never the fit's un-truncated parameters).  Decode is canonical arithmetic, bit-identical on the generic
+    and MFMA paths and on a window's crop, so the difference coded here is the difference the decoder will see.  Before
+    the body is handed back it is decoded into a copy of recon and the bound is checked on every sample."""
+    from . import container, resid
+    cfg = cfg or FeatCfg.from_constants()
+    dev = torch.device(device)
+    msb_d = fit_result.msb_device
+    C, H, W = msb_d.shape
+    orig_d = ops.to_device_u16(_as_planes(img), dev)
+    if tuple(orig_d.shape) != (C, H, W):
+        raise ValueError(f"the original is {tuple(orig_d.shape)}, the fit's planes are {(C, H, W)}")
+    geom = ops.FeatureGeometry(C, H, W, K, D, fit_result.msb_max, cfg, dev)
+    net = ops.make_net(geom.F, base_channel, C, num_layers, cfg.act)
+    params = container.decode_weights(nn_payload, expected=ops.param_count(net))
+    p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
+    recon = ops.decode_fused(geom, net, msb_d, p, path=path).contiguous()
+    body = resid.encode(orig_d, recon, tau)
+    check = resid.apply(body, recon.clone())
+    err = int((orig_d.to(torch.int32) & 0xFFFF).sub_(check.to(torch.int32) & 0xFFFF).abs_().max().item())
+    if err > tau:
+        raise ops._lib.LbdrnError(f"residual layer: max error {err} after decoding the body, {tau} was asked for; no bitstream is written")
+    return body, err
+
+
+def residual_apply(body, recon_d, rect=None):
+    """Apply an LBR1 body to recon_d in place: the [C][h][w] planes (HBM) of rect = (x0, y0, w, h) of the body's tile, None =
+    the whole tile.  Only the blocks that intersect the rectangle are decoded (lbdrn_resid_decode)."""
+    from . import resid
+    return resid.apply(body, recon_d, rect)
 
 
 # ---------------------------------------------------------------- a window of a scene (decode.py --window)
@@ -728,10 +769,12 @@ def window_pieces(width, height, split_ratio, window, D):
     return pieces
 
 
-def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, take=None):
+def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, take=None, enhance=True):
     """The pieces of decode_window(): -> (scene (width, height), [(WindowPiece, [C][yb-ya][xb-xa] device tensor), ...]).
     take(k, piece) -> bool: which of the touched tiles (k counts them in tile order) this caller decodes (decode.py deals
-    them over its ranks); the others are skipped like the tiles the window does not touch."""
+    them over its ranks); the others are skipped like the tiles the window does not touch.  enhance: a file with a
+    residual layer has it applied to each piece through the layer's rectangle argument -- only the blocks the piece touches
+    are decoded -- and the result equals that crop of the whole enhanced decode; False gives the base reconstruction."""
     from . import container
     from .features import window_tables
     bitstream = bytes(bitstream) if not isinstance(bitstream, (bytes, memoryview)) else bitstream
@@ -742,6 +785,7 @@ def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO,
     if activation is not None:                                         # the file says which network it holds (decode.py)
         cfg.activation = activation
     dev = torch.device(device)
+    layer = container.unpack_residual_trailer(bitstream) if enhance else None
     offsets = [n_hdr]
     for t in range(split_ratio * split_ratio):                         # a tile is reached without reading the ones before it
         offsets.append(offsets[-1] + nn_list[t] + base_list[t])
@@ -772,18 +816,21 @@ def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO,
         net = ops.make_net(geom.F, bc, C, nl, cfg.act)
         p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
         rec = ops.decode_fused(geom, net, crop, p, path=path)
-        out.append((pc, rec[:, pc.top:pc.top + pc.yb - pc.ya, pc.left:pc.left + pc.xb - pc.xa]))
+        rec = rec[:, pc.top:pc.top + pc.yb - pc.ya, pc.left:pc.left + pc.xb - pc.xa]
+        if layer is not None:
+            rec = residual_apply(layer[1][pc.tile], rec.contiguous(), (pc.xa, pc.ya, pc.xb - pc.xa, pc.yb - pc.ya))
+        out.append((pc, rec))
     return (width, height), out
 
 
-def decode_window(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, keep_on_device=True):
+def decode_window(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, keep_on_device=True, enhance=True):
     """Reconstruct window = (x0, y0, w, h) (scene pixels) of the scene a .bin holds -> uint16 [C][h][w], bit-identical to
     that crop of the whole reconstruction (decode.py), as a device tensor (uint16 bits in int16 storage, like every plane
     here) or, with keep_on_device=False, as numpy.  Tiles the window does not touch are skipped by the byte sizes the header
     lists: no weight stream, no MSB payload and no kernel runs for them.  A touched tile's MSB payload is decoded whole
     and cropped with a margin of D (window_pieces); its maximum, K, D, the colour switches and the activation are the
     tile's, and with USE_COORDINATES the crop brings the tile's table rows and columns (features.window_tables)."""
-    _, parts = decode_window_pieces(bitstream, window, device, path, cfg)
+    _, parts = decode_window_pieces(bitstream, window, device, path, cfg, enhance=enhance)
     x0, y0, w, h = (int(v) for v in window)
     out = None
     for pc, rec in parts:

@@ -1,4 +1,5 @@
-""".bin container of the codec: header (a12) + per tile the network payload and the MSB payload.
+""".bin container of the codec: header (a12) + per tile the network payload and the MSB payload (+ behind them, with
+encode.py --max-error, the residual-layer trailer: pack_residual_trailer).
 
 Header layout (ref encode.py:37-64, decode.py:25-53), big-endian:
   hdr_len:u8  split_ratio:u8  width:u16  height:u16  (K<<4)|D:u8  (log2(bc)<<4)|nl:u8
@@ -91,6 +92,57 @@ def unpack_header(buf):
     pos += 3 * tiles
     base = [struct.unpack_from(">I", buf, pos + 4 * i)[0] for i in range(tiles)]
     return n, sr, width, height, kd >> 4, 1 << (bcnl >> 4), bcnl & 15, kd & 15, nn, base
+
+
+# ---------------------------------------------------------------- residual-layer trailer (encode.py --max-error)
+
+RESID_TRAILER_MAGIC = b"LBRT"
+RESID_TRAILER_VERSION = 1
+
+
+def residual_trailer_offset(buf):
+    """Where a residual-layer trailer starts if the file has one: behind the header and every payload the header lists.  A
+    file without a layer ends exactly there; the reference's reader and older readers of this package never look further."""
+    n, _, _, _, _, _, _, _, nn, base = unpack_header(buf)
+    return n + sum(nn) + sum(base)
+
+
+def pack_residual_trailer(tau, bodies):
+    """magic 'LBRT' | version u8 | tau u16 | one u32 size per tile | the tiles' LBR1 bodies in tile order (big-endian, like the
+    header).  The header itself is untouched: its bytes, and the refusal of unknown extension flags, stay as they are."""
+    if not 0 <= int(tau) <= 65535:
+        raise OverflowError(f"max error {tau} does not fit its trailer field (0..65535)")
+    out = RESID_TRAILER_MAGIC + struct.pack(">BH", RESID_TRAILER_VERSION, int(tau))
+    for b in bodies:
+        if not 0 <= len(b) < 1 << 32:
+            raise OverflowError(f"residual body of {len(b)} bytes does not fit 4 bytes")
+        out += struct.pack(">I", len(b))
+    return out + b"".join(bytes(b) for b in bodies)
+
+
+def unpack_residual_trailer(buf):
+    """-> (tau, [LBR1 body per tile]) of a .bin with a residual layer, None for a file that ends behind its listed payloads.
+    Anything else behind them -- another magic, a newer version, sizes that do not fill the file -- raises."""
+    off = residual_trailer_offset(buf)
+    if len(buf) == off:
+        return None
+    if len(buf) < off:
+        raise ValueError(f"bitstream of {len(buf)} bytes is shorter than the {off} its header lists")
+    tiles = buf[1] * buf[1]
+    if len(buf) < off + 7 + 4 * tiles or bytes(buf[off:off + 4]) != RESID_TRAILER_MAGIC:
+        raise ValueError(f"{len(buf) - off} bytes behind the listed payloads are not a residual-layer trailer")
+    version, tau = struct.unpack_from(">BH", buf, off + 4)
+    if version != RESID_TRAILER_VERSION:
+        raise ValueError(f"residual-layer trailer version {version}: written by a newer version of this package")
+    sizes = struct.unpack_from(f">{tiles}I", buf, off + 7)
+    pos = off + 7 + 4 * tiles
+    if pos + sum(sizes) != len(buf):
+        raise ValueError(f"residual-layer trailer lists {sum(sizes)} bytes of bodies, the file holds {len(buf) - pos}")
+    bodies = []
+    for n in sizes:
+        bodies.append(bytes(buf[pos:pos + n]))
+        pos += n
+    return tau, bodies
 
 
 # ---------------------------------------------------------------- weights payload (a10)
