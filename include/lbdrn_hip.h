@@ -181,7 +181,8 @@ int lbdrn_eval_sse(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t *im
  * with 32-bit offsets: where they would pass 2 GiB (about 0.9 million rows per minibatch at the headline shape)
  * LBDRN_PATH_MFMA answers LBDRN_E_UNSUPPORTED and LBDRN_PATH_AUTO runs the generic step (same tolerance contract).
  * Which shapes have a fused step: bc = 64 with one or two hidden layers (Sine or ReLU) and up to 256 multiplied features
- * (lbdrn_train_step_features), three hidden layers (Sine) up to F = 256; bc = 64, two hidden layers, Sine or ReLU, with 256 <
+ * (lbdrn_train_step_features), three hidden layers (Sine) up to F = 160 (ten 16-wide strips of dW_0: beyond, the tile kernel's
+ * LDS map passes 160 KB and the shape steps on the generic kernels); bc = 64, two hidden layers, Sine or ReLU, with 256 <
  * features <= 384 -- D = 3 windows on 6, 7 or 8 bands with relative colours -- on one kernel that serves a lone fit and
  * groups alike (W_0 through a ring in LDS: DESIGN.md 11; its slabs reach 2 GiB at about 573,000 rows per minibatch);
  * bc = 128 / 256 up to the same 256.  Every other shape runs on the generic kernels under LBDRN_PATH_AUTO. */

@@ -122,13 +122,14 @@ def test_apply_fuzz_streaming_kernel_equals_generic_and_oracle(dev):
 
 def test_train_fuzz_mfma_matches_generic(dev):
     rng = np.random.default_rng(77)
-    done = 0
+    done = skipped_input = skipped_unsupported = 0
     for it in range(16 * SOAK):
         C, H, W, K, D, bc, nl, cfg, img = _random_case(rng, train=True)
         F = cfg.feature_dim(C, D)
         msb = img >> K
         mx = int(msb.max())
-        if mx == 0 or F > 256:
+        if mx == 0 or F > 256:   # (an all-zero MSB plane, or a width this fuzz does not draw for: no library call was made)
+            skipped_input += 1
             continue
         geom = ops.FeatureGeometry(C, H, W, K, D, mx, cfg, dev)
         net = ops.make_net(F, 64, C, nl, cfg.act)
@@ -163,9 +164,13 @@ def test_train_fuzz_mfma_matches_generic(dev):
             np.testing.assert_allclose(la, lb, rtol=5e-5, err_msg=str(tag))
             assert np.linalg.norm(pa - pb) <= 0.01 * 1e-3 * nsteps * np.sqrt(len(pa)), tag
             assert np.isfinite(pa).all(), tag
-        except ops._lib.LbdrnError:
+        except ops._lib.LbdrnError as e:   # only "this shape has no fused step" skips a case; any other failure is one
+            if e.code != ops._lib.E_UNSUPPORTED:
+                raise
+            skipped_unsupported += 1
             continue
         done += 1
+    assert done + skipped_input + skipped_unsupported == 16 * SOAK, (done, skipped_input, skipped_unsupported)
     assert done >= 6, done
 
 

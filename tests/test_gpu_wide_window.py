@@ -10,6 +10,7 @@ import torch
 import oracle as O
 from lbdrn_hip import codec, ops
 from lbdrn_hip.features import FeatCfg
+from train_step_f64 import f64_steps
 
 pytestmark = pytest.mark.gpu
 GEN, MFMA, AUTO = ops._lib.PATH_GENERIC, ops._lib.PATH_MFMA, ops.PATH_AUTO
@@ -41,32 +42,8 @@ def _bits_equal(a, b):
 
 
 def _f64_steps(x, t, params0, batches, F, bc, C, lrs, act):
-    """The teacher-forced updates in float64 numpy (LBDRNmodel.py:79-82, LBDRNloss.py:9, torch/optim/adam.py)."""
-    if act == "relu":
-        fwd, der = (lambda z: np.maximum(z, 0.0)), (lambda z: (z > 0).astype(np.float64))
-    else:
-        fwd, der = (lambda z: np.sin(30 * z)), (lambda z: 30 * np.cos(30 * z))
-    x, t = x.astype(np.float64), t.astype(np.float64)
-    p = params0.astype(np.float64)
-    m, v = np.zeros_like(p), np.zeros_like(p)
-    o1, o2, o3, o4, o5 = bc * F, bc * F + bc, bc * F + bc + bc * bc, bc * F + 2 * bc + bc * bc, bc * F + 2 * bc + bc * bc + C * bc
-    for s, b in enumerate(batches):
-        W0, b0, W1, b1 = p[:o1].reshape(bc, F), p[o1:o2], p[o2:o3].reshape(bc, bc), p[o3:o4]
-        W2, b2 = p[o4:o5].reshape(C, bc), p[o5:]
-        xb, tb = x[b], t[b]
-        z0 = xb @ W0.T + b0; h0 = fwd(z0)
-        z1 = h0 @ W1.T + b1; h1 = fwd(z1)
-        y = 1 / (1 + np.exp(-(h1 @ W2.T + b2)))
-        d = y - tb
-        dz2 = 2 * d / d.size * y * (1 - y)
-        dz1 = (dz2 @ W2) * der(z1)
-        dz0 = (dz1 @ W1) * der(z0)
-        g = np.concatenate([(dz0.T @ xb).ravel(), dz0.sum(0), (dz1.T @ h0).ravel(), dz1.sum(0), (dz2.T @ h1).ravel(), dz2.sum(0)])
-        m = 0.9 * m + 0.1 * g
-        v = 0.999 * v + 0.001 * g * g
-        st = s + 1
-        p = p - (lrs[s] / (1 - 0.9 ** st)) * m / (np.sqrt(v) / np.sqrt(1 - 0.999 ** st) + 1e-8)
-    return p, m, v
+    """The teacher-forced updates in float64 numpy (tests/train_step_f64.py)."""
+    return f64_steps(x, t, params0, batches, F, bc, C, lrs, act=act, nl=2)
 
 
 def _teacher_forced(dev, img, cfg, params0, batches, lrs, rows, path, alone, losses_ref=None):
