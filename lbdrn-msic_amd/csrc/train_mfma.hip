@@ -110,6 +110,12 @@ static FeatMap centre_skipping_map(const lbdrn_geom& g, const lbdrn_net& net)
     return FeatMap{net.F, 0, 0, 0};
 }
 
+// TrainPlan::wave, which fused step runs a shape: a function of the shape only (the choice fixes the row-matrix layout that
+// lbdrn_train_prepare builds and lbdrn_train_epoch reads)
+constexpr int STEP_TILE = 0;     // the 8-wave tile kernel k_train_mfma (nl = 3, Sine)
+constexpr int STEP_STREAM = 2;   // k_train_stream / k_train_split (nl <= 2); steps groups of fits
+
+// Passed to the kernels by value: the layout is theirs (kernarg), the unused fields included.
 struct TrainPlan {
     FeatMap fm;
     int LQ;                    // layer-0 quarter length = MFMA steps of layer 0 (fm.Fe <= 4*LQ)
@@ -119,19 +125,56 @@ struct TrainPlan {
     int64_t NP;
     int64_t offW[5], offB[5];  // canonical parameter offsets per layer (index nl = last layer)
     int pk_w0, pk_wh, pk_wl, pack_floats;  // fragment-order buffer (floats)
-    int wave;                  // 2: k_train_stream, 0: the tile kernel (fragment orders differ, see frag_pos)
-    int pk_wht, pk_wlt;        // wave-local kernel: W_l^T and W_last^T fragments for the backward products
-    int w_dp, w_df;            // 64 / (RP/4) and 64 % (RP/4): chunk walk of the row copy
-    int wave_lds_floats;
+    int wave;                  // STEP_STREAM or STEP_TILE (fragment orders differ, see frag_pos)
+    int pk_wht, pk_wlt;        // streamed step: W_l^T and W_last^T fragments for the backward products
+    int w_dp, w_df;            // unused (the retired wave kernel's row copy); kept for the layout, always 0
+    int wave_lds_floats;       // k_train_stream's LDS map (stream_lds)
     int sl_hid, sl_out, sl_bias, slab_floats;  // slab (tile order) section starts, in floats
-    int lds_x, lds_xt, lds_h, lds_ht, lds_z, lds_zt, lds_zo, lds_zot, lds_pix, lds_red, lds_floats;
+    int lds_x, lds_xt, lds_h, lds_ht, lds_z, lds_zt, lds_zo, lds_zot, lds_pix, lds_red, lds_floats;   // the tile kernel's LDS map: nothing else reads it
 };
 
-__host__ __device__ constexpr int stream_rp(int LQ);
-// the layer-0 quarter length of the one shape above 256 features that has a fused step (nl = 2; 256 < Fe <= 384): it runs
-// on k_train_split only -- neither k_train_stream's LDS map nor the tile kernel's fits it --, alone or in a group
+// ---- the instances of the fused bc = 64 step: every kernel that is compiled, each list stated once.  The dispatch, split_available
+// and the LQ that make_train_plan picks all come from these lists (rows in ascending LQ); DESIGN.md 12 has a shape for every row.
+//
+// k_train_stream<LQ, NL, STREAM_PD, NT0C, ACT>, both activations.  NT0C = 0: the weight-gradient loop, any number of strips;
+// NT0C > 0: the straight-line schedule of exactly NT0C strips -- the shapes BASELINE.json names (F = 200: 12 strips of
+// features that can differ from zero, F = 250: 16), the reference's 4-band shape (F = 100, 96 that can differ from zero: 6) and LQ 52's only strip count.
+// (No 52/2/0: LQ 52 is Fe 193..208 and every such Fe has 13 strips, so 52/2/13 takes them all.)
+#define STREAM_INSTANCES(X) \
+    X(16, 1, 0) X(16, 2, 0)              \
+    X(24, 1, 0) X(24, 2, 0) X(24, 2, 6)  \
+    X(32, 1, 0) X(32, 2, 0)              \
+    X(48, 1, 0) X(48, 2, 0) X(48, 2, 12) \
+    X(52, 1, 0)             X(52, 2, 13) \
+    X(64, 1, 0) X(64, 2, 0) X(64, 2, 16)
+// k_train_split<LQ, NT0C, ACT> (nl = 2), both activations: beside k_train_stream for a fit that has the device to itself (same
+// bits: train_split.inc) -- the two shapes BASELINE.json names and the 4-band shape of the reference's own image list
+// (run.sh:14-28) --, and the one step of 256 < Fe <= 384 (D = 3 windows on 6..8 bands; 24 strips, the slots past Fe zero), which
+// neither k_train_stream's LDS map nor the tile kernel's fits: LQ 96 runs on k_train_split only, alone or in a group.
+#define SPLIT_INSTANCES(X) X(24, 6) X(48, 12) X(64, 16) X(96, 24)
 constexpr int SPLIT_WIDE_LQ = 96;
-struct StreamLds;
+// k_train_mfma<LQ, NL>, the Sine network's nl = 3.  (No nl = 1, 2: such a shape steps on k_train_stream whenever Fe <= 256 -- its
+// LDS map stays under 160 KB at every LQ, asserted below the kernel --, and past that F > 256, which this kernel refuses too.
+// No 64/3: at LQ 64 the LDS map of nl = 3 is (36,464 + 576 NT0) floats against 40,960, so NT0 <= 7 and F <= 112, while LQ 64 needs
+// F > 208 or F + C > 212 with C <= 16.)
+#define TILE_INSTANCES(X) X(16, 3) X(32, 3) X(52, 3)
+
+// What the rest reads off the lists (0: no such row).  stream_nt0c: the schedule that steps (lq, nl) at nt0 strips -- nt0 where the
+// list has that row, otherwise the loop; stream_lq / tile_lq: the smallest LQ that holds the shape; split_nt0c: the strips at lq.
+#define X(LQ, NL, NT0C) if (lq == LQ && nl == NL && nt0 == NT0C) return NT0C;
+constexpr int stream_nt0c(int lq, int nl, int nt0) { STREAM_INSTANCES(X) return 0; }
+#undef X
+#define X(LQ, NL, NT0C) if (nl == NL && fe <= 4 * LQ) return LQ;
+constexpr int stream_lq(int fe, int nl) { STREAM_INSTANCES(X) return 0; }
+#undef X
+#define X(LQ, NT0C) if (lq == LQ) return NT0C;
+constexpr int split_nt0c(int lq) { SPLIT_INSTANCES(X) return 0; }
+#undef X
+#define X(LQ, NL) static_assert(4 * LQ % 16 == 0, "16 NT0 > XP: dW0's last strip passes the X row"); if (nl == NL && F <= 4 * LQ && RP <= 4 * LQ + 4) return LQ;
+constexpr int tile_lq(int F, int RP, int nl) { TILE_INSTANCES(X) return 0; }
+#undef X
+
+__host__ __device__ constexpr int stream_rp(int LQ);
 static int stream_lds_total(int LQ, int NL);
 
 static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan* out)
@@ -139,28 +182,24 @@ static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan
     if ((net.act != LBDRN_ACT_SINE && net.act != LBDRN_ACT_RELU) || net.bc != TBC || net.nl < 1 || net.nl > 3 || net.C > 16 || net.F < 1) return false;
     if (net.act == LBDRN_ACT_RELU && net.nl > 2) return false;   // (ReLU: the streamed step and k_train_split; the nl = 3 tile kernel is the Sine network's)
     TrainPlan p;
-    p.RP = (net.F + net.C + 3) / 4 * 4;
-    p.LQ = 0;
-    p.fm = FeatMap{net.F, 0, 0, 0};
-    // which fused step runs the shape: 2 = k_train_stream, 0 = the 8-wave tile kernel k_train_mfma (nl = 3).  A function of
-    // the shape only (the choice fixes the row-matrix layout that lbdrn_train_prepare builds and lbdrn_train_epoch reads)
-    int kind = net.nl <= 2 ? 2 : 0;
-    if (kind == 2) {   // the streamed step: features in 4 LQ slots, labels in a group of their own
+    p.wave = net.nl <= 2 ? STEP_STREAM : STEP_TILE;
+    if (p.wave == STEP_STREAM) {   // features in 4 LQ slots, labels in a group of their own; the matrix in the order layer 0 eats it (train_stream.inc)
         p.fm = centre_skipping_map(g, net);
-        for (int lq : {16, 24, 32, 48, 52, 64})   // (24: the reference's 4-band shape -- F = 100, 96 features that can differ from zero)
-            if (p.fm.Fe <= 4 * lq) { p.LQ = lq; break; }
-        // 256 < Fe <= 384 at nl = 2 (D = 3 windows on 6..8 bands): k_train_split alone, with W_0 in a ring (train_split.inc)
-        if (!p.LQ && net.nl == 2 && p.fm.Fe <= 4 * SPLIT_WIDE_LQ) p.LQ = SPLIT_WIDE_LQ;
-        if (!p.LQ || (p.LQ != SPLIT_WIDE_LQ && (size_t)stream_lds_total(p.LQ, net.nl) * 4 > 160 * 1024)) { kind = 0; p.LQ = 0; p.fm = FeatMap{net.F, 0, 0, 0}; }
+        p.LQ = stream_lq(p.fm.Fe, net.nl);
+        if (!p.LQ && net.nl == 2 && p.fm.Fe <= 4 * SPLIT_WIDE_LQ) p.LQ = SPLIT_WIDE_LQ;   // k_train_split alone, with W_0 in a ring (train_split.inc)
+        if (!p.LQ) return false;
+        p.NT0 = p.LQ == SPLIT_WIDE_LQ ? split_nt0c(SPLIT_WIDE_LQ) : (p.fm.Fe + 15) / 16;
+        p.RP = stream_rp(p.LQ);
+        p.wave_lds_floats = p.LQ == SPLIT_WIDE_LQ ? 0 : stream_lds_total(p.LQ, net.nl);
+    } else {
+        p.fm = FeatMap{net.F, 0, 0, 0};
+        p.RP = (net.F + net.C + 3) / 4 * 4;
+        p.LQ = tile_lq(net.F, p.RP, net.nl);
+        if (!p.LQ) return false;
+        p.NT0 = (net.F + 15) / 16;
+        p.wave_lds_floats = 0;
     }
-    if (kind != 2 && net.act != LBDRN_ACT_SINE) return false;
-    if (kind != 2)
-        for (int lq : {16, 32, 52, 64})
-            if (net.F <= 4 * lq && p.RP <= 4 * lq + 4) { p.LQ = lq; break; }
-    if (!p.LQ) return false;
     p.XP = 4 * p.LQ + 4;
-    p.NT0 = p.LQ == SPLIT_WIDE_LQ ? SPLIT_WIDE_LQ / 4 : (p.fm.Fe + 15) / 16;   // (the wide step's one instance: 24 strips, the slots past Fe zero)
-    if (kind != 2 && 16 * p.NT0 > p.XP) return false;
     p.NP = param_count(net);
     int64_t o = 0;
     for (int l = 0; l < net.nl; ++l) {
@@ -178,17 +217,12 @@ static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan
     p.pk_wlt = k; k += 16 * 64;
     p.pack_floats = k;
     p.w_dp = p.w_df = 0;
-    p.wave_lds_floats = 0;
-    if (kind == 2) {
-        p.RP = stream_rp(p.LQ);   // the matrix in the order layer 0 eats it (train_stream.inc)
-        p.wave_lds_floats = p.LQ == SPLIT_WIDE_LQ ? 0 : stream_lds_total(p.LQ, net.nl);
-    }
-    p.wave = kind;
     int s = 4 * p.NT0 * 256;
     p.sl_hid = s; s += (net.nl - 1) * 16 * 256;
     p.sl_out = s; s += 4 * 256;
     p.sl_bias = s; s += net.nl * TBC + 16;
     p.slab_floats = (s + 127) / 128 * 128;  // multiple of 4*RED_LANES
+    // the tile kernel's LDS map (filled for every plan: the struct is one layout).  Its 160 KB bound is what refuses F = 161..208 at nl = 3
     int f = 0;
     p.lds_x = f; f += TB * p.XP;
     p.lds_xt = f; f += 16 * p.NT0 * TP;
@@ -201,7 +235,7 @@ static bool make_train_plan(const lbdrn_geom& g, const lbdrn_net& net, TrainPlan
     p.lds_pix = f; f += TB;
     p.lds_red = f; f += 16;
     p.lds_floats = f;
-    if (kind == 0 && (size_t)f * 4 > 160 * 1024) return false;
+    if (p.wave == STEP_TILE && (size_t)f * 4 > 160 * 1024) return false;
     *out = p;
     return true;
 }
@@ -224,7 +258,7 @@ bool mfma_train_supported(const lbdrn_geom& g, const lbdrn_net& net, int bs)
 bool mfma_train_takes_groups(const lbdrn_geom& g, const lbdrn_net& net)
 {
     TrainPlan p;
-    return make_train_plan(g, net, &p) && p.wave == 2;
+    return make_train_plan(g, net, &p) && p.wave == STEP_STREAM;
 }
 
 
@@ -433,11 +467,11 @@ __global__ void __launch_bounds__(256)
 }
 
 // canonical parameter index -> positions in the fragment-order buffer (or -1: not packed): .x = the copy the forward
-// products read, .y = the transposed copy the wave-local kernel's backward products read.
+// products read, .y = the transposed copy the streamed step's backward products read.
 // Quarter-K order: MFMA step s of lane quarter q multiplies k = q*L + s.  Four consecutive steps of a
 // lane are adjacent ([step/4][lane][step%4]) so that a fragment fetch is one 16-byte load per four steps.
-// Tile kernel (p.wave == 0): hidden and output layers walk k = 16q + s as well.
-// Wave-local kernel (p.wave == 1): the B operand of a hidden / output product is the previous layer's accumulator
+// Tile kernel (p.wave == STEP_TILE): hidden and output layers walk k = 16q + s as well.
+// Streamed step (p.wave == STEP_STREAM): the B operand of a hidden / output product is the previous layer's accumulator
 // as it stands in registers (lane quarter q, tile t, register r holds unit 16t + 4q + r), so step (t, r) multiplies
 // k = 16t + 4q + r; the backward products take W^T the same way (k = output unit of the layer).
 __device__ __forceinline__ int2 frag_pos(int64_t idx, const TrainPlan& p, int F, int nl, int C)
@@ -1168,6 +1202,10 @@ int train_profile_mode(int mode)
 #include "train_stream.inc"
 
 static int stream_lds_total(int LQ, int NL) { return stream_lds(LQ, NL).total; }
+// every streamed instance's LDS map fits a workgroup's 160 KB: make_train_plan has no other kernel to fall back to
+#define X(LQ, NL, NT0C) static_assert(stream_lds(LQ, NL).total * 4 <= 160 * 1024, "k_train_stream's LDS map passes 160 KB");
+STREAM_INSTANCES(X)
+#undef X
 
 #include "train_split.inc"
 
@@ -1207,16 +1245,8 @@ static int launch_train(const TrainArgs& A, int nwg, hipStream_t s)
     return 0;
 }
 
-template <int LQ>
-static int dispatch_nl(const TrainArgs& A, int nwg, hipStream_t s)
-{
-    if (A.net.nl == 1) return launch_train<LQ, 1>(A, nwg, s);
-    if (A.net.nl == 2) return launch_train<LQ, 2>(A, nwg, s);
-    return launch_train<LQ, 3>(A, nwg, s);
-}
-
 template <int LQ, int NL, int NT0C, int ACT>
-static int launch_stream_act(const TrainArgs& A, int nwg, int count, hipStream_t s)
+static int launch_stream(const TrainArgs& A, int nwg, int count, hipStream_t s)
 {
     auto kern = k_train_stream<LQ, NL, STREAM_PD, NT0C, ACT>;
     static std::atomic<unsigned long long> configured{0};
@@ -1226,48 +1256,8 @@ static int launch_stream_act(const TrainArgs& A, int nwg, int count, hipStream_t
     return 0;
 }
 
-template <int LQ, int NL, int NT0C>
-static int launch_stream(const TrainArgs& A, int nwg, int count, hipStream_t s)
-{
-    return A.net.act == LBDRN_ACT_RELU ? launch_stream_act<LQ, NL, NT0C, LBDRN_ACT_RELU>(A, nwg, count, s)
-                                       : launch_stream_act<LQ, NL, NT0C, LBDRN_ACT_SINE>(A, nwg, count, s);
-}
-
-static int dispatch_stream(const TrainArgs& A, int nwg, int count, hipStream_t s)
-{
-    const bool one = A.net.nl == 1;
-    // the shapes BASELINE.json names (F = 200: 12 strips of features that can differ from zero, F = 250: 16) and the
-    // reference's 4-band shape (F = 100: 6) run the straight-line weight-gradient schedule
-    switch (A.p.LQ) {
-        case 16: return one ? launch_stream<16, 1, 0>(A, nwg, count, s) : launch_stream<16, 2, 0>(A, nwg, count, s);
-        case 24:
-            if (!one && A.p.NT0 == 6) return launch_stream<24, 2, 6>(A, nwg, count, s);
-            return one ? launch_stream<24, 1, 0>(A, nwg, count, s) : launch_stream<24, 2, 0>(A, nwg, count, s);
-        case 32: return one ? launch_stream<32, 1, 0>(A, nwg, count, s) : launch_stream<32, 2, 0>(A, nwg, count, s);
-        case 48:
-            if (!one && A.p.NT0 == 12) return launch_stream<48, 2, 12>(A, nwg, count, s);
-            return one ? launch_stream<48, 1, 0>(A, nwg, count, s) : launch_stream<48, 2, 0>(A, nwg, count, s);
-        case 52:
-            if (!one && A.p.NT0 == 13) return launch_stream<52, 2, 13>(A, nwg, count, s);
-            return one ? launch_stream<52, 1, 0>(A, nwg, count, s) : launch_stream<52, 2, 0>(A, nwg, count, s);
-        default:
-            if (!one && A.p.NT0 == 16) return launch_stream<64, 2, 16>(A, nwg, count, s);
-            return one ? launch_stream<64, 1, 0>(A, nwg, count, s) : launch_stream<64, 2, 0>(A, nwg, count, s);
-    }
-}
-
-// the shapes that have k_train_split beside k_train_stream (same bits: train_split.inc) -- the two BASELINE.json names and
-// the 4-band shape of the reference's own image list (run.sh:14-28)
-static bool split_available(const TrainPlan& p, const lbdrn_net& net)
-{
-    return p.wave == 2 && net.nl == 2 && ((p.LQ == 48 && p.NT0 == 12) || (p.LQ == 64 && p.NT0 == 16) || (p.LQ == 24 && p.NT0 == 6) ||
-                                          (p.LQ == SPLIT_WIDE_LQ && p.NT0 == SPLIT_WIDE_LQ / 4));
-}
-// ... and the wide shape has nothing else: every step of it, alone or in a group, one row or many, is k_train_split's
-static bool split_only(const TrainPlan& p) { return p.LQ == SPLIT_WIDE_LQ; }
-
 template <int LQ, int NT0C, int ACT>
-static int launch_split_act(const TrainArgs& A, int nwg, int count, hipStream_t s)
+static int launch_split(const TrainArgs& A, int nwg, int count, hipStream_t s)
 {
     auto kern = k_train_split<LQ, NT0C, ACT>;
     constexpr int bytes = split_lds(LQ).total * 4;
@@ -1278,28 +1268,32 @@ static int launch_split_act(const TrainArgs& A, int nwg, int count, hipStream_t 
     return 0;
 }
 
-template <int LQ, int NT0C>
-static int launch_split(const TrainArgs& A, int nwg, int count, hipStream_t s)
+// k_train_split steps beside k_train_stream where the split list has the shape's (LQ, NT0) ...
+static bool split_available(const TrainPlan& p, const lbdrn_net& net)
 {
-    return A.net.act == LBDRN_ACT_RELU ? launch_split_act<LQ, NT0C, LBDRN_ACT_RELU>(A, nwg, count, s)
-                                       : launch_split_act<LQ, NT0C, LBDRN_ACT_SINE>(A, nwg, count, s);
+    return p.wave == STEP_STREAM && net.nl == 2 && split_nt0c(p.LQ) == p.NT0;
 }
+// ... and the wide shape has nothing else: every step of it, alone or in a group, one row or many, is k_train_split's
+static bool split_only(const TrainPlan& p) { return p.LQ == SPLIT_WIDE_LQ; }
 
-static int dispatch_split(const TrainArgs& A, int nwg, int count, hipStream_t s)
+// The one place a kernel of the three lists is named for launching.  A (LQ, nl, NT0) that no row names is one make_train_plan does
+// not plan: it is refused, never stepped on some other instance.
+static int dispatch_train(const TrainArgs& A, int nwg, int count, bool split, hipStream_t s)
 {
-    if (A.p.LQ == SPLIT_WIDE_LQ) return launch_split<SPLIT_WIDE_LQ, SPLIT_WIDE_LQ / 4>(A, nwg, count, s);
-    return A.p.LQ == 48 ? launch_split<48, 12>(A, nwg, count, s) : A.p.LQ == 24 ? launch_split<24, 6>(A, nwg, count, s) : launch_split<64, 16>(A, nwg, count, s);
-}
-
-static int dispatch_train(const TrainArgs& A, int nwg, int count, hipStream_t s)
-{
-    if (A.p.wave == 2) return dispatch_stream(A, nwg, count, s);
-    switch (A.p.LQ) {
-        case 16: return dispatch_nl<16>(A, nwg, s);
-        case 32: return dispatch_nl<32>(A, nwg, s);
-        case 52: return dispatch_nl<52>(A, nwg, s);
-        default: return dispatch_nl<64>(A, nwg, s);
-    }
+    const TrainPlan& p = A.p;
+    const int nl = A.net.nl, nt0c = stream_nt0c(p.LQ, nl, p.NT0);
+    const bool relu = A.net.act == LBDRN_ACT_RELU;
+#define ACTS(launch, ...) return relu ? launch<__VA_ARGS__, LBDRN_ACT_RELU>(A, nwg, count, s) : launch<__VA_ARGS__, LBDRN_ACT_SINE>(A, nwg, count, s);
+#define SPLIT(lq, c) if (split && p.LQ == lq && p.NT0 == c) ACTS(launch_split, lq, c)
+#define STREAM(lq, n, c) if (!split && p.wave == STEP_STREAM && p.LQ == lq && nl == n && nt0c == c) ACTS(launch_stream, lq, n, c)
+#define TILE(lq, n) if (!split && p.wave == STEP_TILE && p.LQ == lq && nl == n) return launch_train<lq, n>(A, nwg, s);
+    SPLIT_INSTANCES(SPLIT) STREAM_INSTANCES(STREAM) TILE_INSTANCES(TILE)
+#undef ACTS
+#undef SPLIT
+#undef STREAM
+#undef TILE
+    set_error("no fused step is built for LQ = %d, nl = %d, NT0 = %d%s", p.LQ, nl, p.NT0, split ? " (k_train_split)" : "");
+    return LBDRN_E_UNSUPPORTED;
 }
 
 // Build the per-image state of the fused training path in the caller's workspace: the
@@ -1313,7 +1307,7 @@ int mfma_train_prepare(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t
     if (make_train_plan(g, net, &p)) {
         const TrainWsLayout L = train_ws_layout(g, net, p, bs);
         need = L.total; off_rows = L.off_rows;
-        if (p.wave == 2) LQs = p.LQ;
+        if (p.wave == STEP_STREAM) LQs = p.LQ;
     } else {
         WidePlan wp;
         if (!make_wide_plan(g, net, &wp)) {
@@ -1361,7 +1355,7 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
         return wide_train_epoch(g, net, perm[0], n, bs, params[0], m[0], v[0], step0, lr, losses ? losses[0] : nullptr,
                                 ws[0], ws_bytes, s);
     }
-    if (count < 1 || count > MAX_GROUP || (count > 1 && A.p.wave != 2)) {
+    if (count < 1 || count > MAX_GROUP || (count > 1 && A.p.wave != STEP_STREAM)) {
         set_error("a group of %d fits is not supported by this shape's train kernel", count);
         return LBDRN_E_UNSUPPORTED;
     }
@@ -1412,7 +1406,7 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
         LBDRN_HIP_TRY(hipMemset(tl_buf, 0, (size_t)tl_steps * TL_SLOTS * sizeof(unsigned long long)));
     }
 #endif
-    const int rows_per_wg = A.p.wave ? WB : TB;
+    const int rows_per_wg = A.p.wave == STEP_STREAM ? WB : TB;
     // A fit that has the device to itself (LBDRN_TRAIN_ALONE) steps on k_train_split where the shape has it: 256 workgroups
     // of 32 rows, every CU, two slabs per 64-row group.  The numbers are k_train_stream's bit for bit (train_split.inc).
     const bool split = (alone && count == 1 && split_available(A.p, net)) || split_only(A.p);
@@ -1440,7 +1434,7 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
         const int64_t nextB = std::max<int64_t>(0, std::min<int64_t>(bs, n - first - bs));
         A.stage_in = si > 0 ? stage[si & 1] : nullptr;          // staged by the previous launch
         A.stage_out = nextB > 0 ? stage[(si + 1) & 1] : nullptr;
-        if (A.p.wave) A.stage_in = nullptr, A.stage_out = nullptr;   // the wave-local kernels gather for themselves
+        if (A.p.wave == STEP_STREAM) A.stage_in = nullptr, A.stage_out = nullptr;   // k_train_stream / k_train_split gather for themselves
         A.perm_next = perm[0] + first + bs;
         A.next_n = (int)nextB;
         A.touch_row_bytes = (alone && count == 1) ? TOUCH_ROW_BYTES : 0;   // (LBDRN_TRAIN_ALONE; see k_train_stream's loader wave)
@@ -1448,7 +1442,7 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
         const bool split_now = split && (B >= 2 || split_only(A.p));   // (k_train_split fetches the pixel indices two at a time: a minibatch of ONE
                                                   // row -- the tail of an epoch of n = 1 (mod batch size) rows -- steps on k_train_stream; the same bits.
                                                   // The wide shape's instance fetches them one at a time.)
-        auto train_launch = [&]() { return split_now ? dispatch_split(A, 2 * nwg, count, s) : dispatch_train(A, nwg, count, s); };
+        auto train_launch = [&]() { return dispatch_train(A, split_now ? 2 * nwg : nwg, count, split_now, s); };
         if (int rc = train_launch()) return rc;
         if (g_prof_mode == 2)   // measurement only: the same launch again (it writes the same slabs and loss partials)
             if (int rc = train_launch()) return rc;
@@ -1484,9 +1478,9 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
     }
 #endif
 #ifdef LBDRN_TRAIN_STAMPS
-    if (A.p.wave) {   // diagnostic: mean cycles per phase over the waves of the last step
+    if (A.p.wave == STEP_STREAM) {   // diagnostic: mean cycles per phase over the waves of the last step
         LBDRN_HIP_TRY(hipStreamSynchronize(s));
-        const int nw = ((int)std::min<int64_t>(bs, n) + rows_per_wg - 1) / rows_per_wg * 4 * (A.p.wave == 2 ? count : 1) * (split ? 2 : 1);
+        const int nw = ((int)std::min<int64_t>(bs, n) + rows_per_wg - 1) / rows_per_wg * 4 * count * (split ? 2 : 1);
         std::vector<unsigned long long> h((size_t)nw * 16);
         LBDRN_HIP_TRY(hipMemcpy(h.data(), A.stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         (void)hipFree(A.stamps);
@@ -1507,13 +1501,8 @@ int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net,
                     clk / nw, span / nw, (double)(t1max - t0min) / 100.0, d[1] / nw, d[2] / nw, d[3] / nw, d[4] / nw, d[5] / nw, d[6] / nw,
                     d[7] / nw, d[8] / nw, d[9] / nw, d[10] / nw, (d[11] + d[12]) / nw, d[13] / nw);
         else
-        fprintf(stderr, A.p.wave == 2 ?
-                        "[lbdrn stamps, stream kernel] clock %.0f MHz; wave lifetime %.0f cycles; first start -> last end %.2f us; "
+        fprintf(stderr, "[lbdrn stamps, stream kernel] clock %.0f MHz; wave lifetime %.0f cycles; first start -> last end %.2f us; "
                         "mean cycles: indices + first requests out %.0f | first stage landed %.0f | layer 0 under the stream %.0f | all landed, barrier %.0f | "
-                        "act0 %.0f | hidden+act %.0f | out+loss %.0f | backward %.0f | barrier 3 %.0f | dW0 strips %.0f | dW tail+hidden %.0f | "
-                        "bias sums %.0f | drain %.0f\n" :
-                        "[lbdrn stamps, wave kernel] clock %.0f MHz; wave lifetime %.0f cycles; first start -> last end %.2f us; "
-                        "mean cycles: W0 DMA + rows->LDS %.0f | barrier 1 %.0f | small-matrix requests + layer0 %.0f | barrier 2 %.0f | "
                         "act0 %.0f | hidden+act %.0f | out+loss %.0f | backward %.0f | barrier 3 %.0f | dW0 strips %.0f | dW tail+hidden %.0f | "
                         "bias sums %.0f | drain %.0f\n",
                 clk / nw, span / nw, (double)(t1max - t0min) / 100.0, d[1] / nw, d[2] / nw, d[3] / nw, d[4] / nw, d[5] / nw, d[6] / nw,

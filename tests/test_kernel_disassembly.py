@@ -127,3 +127,32 @@ def test_the_only_build_switches_are_the_measurement_instruments():
             assert names <= instruments, f"{f}: {m.group(0).strip()[:80]} tests {sorted(names - instruments)}"
             seen |= names
     assert seen == instruments, sorted(instruments - seen)
+
+
+def test_the_training_kernels_in_the_library_are_exactly_the_listed_instances(tmp_path):
+    """Kernel symbols only: the k_train_stream<..>, k_train_split<..> and k_train_mfma<..> instances in the shipped library's
+    gfx950 code object are the ones the three lists of csrc/train_mfma.hip name (tests/train_plan_reference.py:
+    built_instances) -- nothing that no shape reaches is compiled, nothing a shape reaches is missing."""
+    import sys
+    so = os.path.join(ROOT, "lbdrn-msic_amd", "liblbdrn_hip.so")
+    if not (os.path.exists(OBJDUMP) and os.path.exists(so)):
+        pytest.skip("llvm-objdump or the library is missing")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import train_plan_reference as R
+    work = tmp_path / "co"
+    work.mkdir()
+    shutil.copy(so, work / "lib.so")
+    subprocess.run([OBJDUMP, "--offloading", "lib.so"], cwd=work, check=True, capture_output=True)   # unbundles next to the input
+    found = set()
+    for co in sorted(work.glob("lib.so.*gfx950")):
+        syms = subprocess.run([OBJDUMP, "--syms", "-C", str(co)], capture_output=True, text=True, check=True).stdout
+        for kernel, args in re.findall(r"\blbdrn::k_train_(stream|split|mfma)<([\d, ]+)>\(", syms):
+            a = [int(x) for x in args.split(",")]
+            if kernel == "stream":      # <LQ, NL, PD, NT0C, ACT>
+                found.add(("stream", a[0], a[1], a[3], R.ACTS[a[4]]))
+            elif kernel == "split":     # <LQ, NT0C, ACT>
+                found.add(("split", a[0], 2, a[1], R.ACTS[a[2]]))
+            else:                       # <LQ, NL>
+                found.add(("tile", a[0], a[1], 0, "sine"))
+    built = set(R.built_instances())
+    assert found == built, (sorted(found - built), sorted(built - found))

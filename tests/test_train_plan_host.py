@@ -1,8 +1,8 @@
-"""The CPU half of the training-instance census (tests/train_plan_reference.py, tests/train_step_f64.py): the constants of
-csrc/train_mfma.hip and csrc/train_stream.inc read out of their text, the restatement of the plan held to what the library
-tells without a device (lbdrn_train_step_features, lbdrn_train_group_size), every reachable instance listed exactly once,
-every claim of unreachability checked over all (F, C), the class boundaries of Fe, the ReLU kink condition on the inputs of
-every ReLU row, and the float64 step held to the reference's fixtures.
+"""The CPU half of the training-instance census (tests/train_plan_reference.py, tests/train_step_f64.py): the instance lists
+and constants of csrc/train_mfma.hip and csrc/train_stream.inc read out of their text, the restatement of the plan held to what
+the library tells without a device (lbdrn_train_step_features, lbdrn_train_group_size), every built instance listed exactly
+once with a real shape, the instances reached over all (F, C) exactly the built ones, the class boundaries of Fe, the ReLU kink
+condition on the inputs of every ReLU row, and the float64 step held to the reference's fixtures.
 
 Nothing here needs a GPU.  tests/test_gpu_train_instances.py steps the table on the device."""
 import ctypes
@@ -23,16 +23,18 @@ RTOL_TRAIN = 1e-5
 
 def test_constants_are_the_ones_the_source_states():
     k = R.source_constants()
-    assert k["STREAM_LQ"] == R.STREAM_LQ == (16, 24, 32, 48, 52, 64)
-    assert k["TILE_LQ"] == R.TILE_LQ == k["TILE_DISPATCH"] == (16, 32, 52, 64)
+    assert k["STREAM"] == R.STREAM and k["SPLIT"] == R.SPLIT and k["TILE"] == R.TILE
+    assert [lq for lq, nl, c in R.STREAM] == sorted(lq for lq, nl, c in R.STREAM)   # make_train_plan takes the first row that holds Fe
+    assert R.STREAM_LQ == (16, 24, 32, 48, 52, 64)
+    assert R.TILE_LQ == (16, 32, 52) and all(nl == 3 for lq, nl in R.TILE)
     assert k["SPLIT_WIDE_LQ"] == R.SPLIT_WIDE_LQ == 96
     assert k["MAX_GROUP"] == R.MAX_GROUP == 4
     assert k["LDS_BOUND"] == R.LDS_BOUND == 163840
-    assert k["STRAIGHT"] == R.STRAIGHT == ((24, 6), (48, 12), (52, 13), (64, 16))
-    assert k["SPLIT"] == R.SPLIT == ((24, 6), (48, 12), (64, 16), (96, 24))
-    # the instances dispatch_stream names: both layer counts of every LQ on the loop, plus the straight-line ones
+    assert R.STRAIGHT == ((24, 6), (48, 12), (52, 13), (64, 16))
+    assert R.SPLIT == ((24, 6), (48, 12), (64, 16), (96, 24)) and dict(R.SPLIT)[R.SPLIT_WIDE_LQ] == 24
+    # the streamed list: both layer counts of every LQ on the loop, plus the straight-line ones -- but no 52/2/0, which nothing reaches
     want = sorted([(lq, nl, 0) for lq in R.STREAM_LQ for nl in (1, 2)] + [(lq, 2, nt) for lq, nt in R.STRAIGHT])
-    assert list(k["STREAM_INSTANCES"]) == want
+    assert sorted(R.STREAM + ((52, 2, 0),)) == want
     for lq, nt in R.STRAIGHT + R.SPLIT:
         assert 16 * nt == 4 * lq                              # a straight-line schedule fills the slots of its LQ
     with open(os.path.join(R.CSRC, "cabi.hip")) as f:
@@ -58,7 +60,7 @@ def test_lds_map_constants_are_the_ones_the_sources_state():
     assert R.stream_lds_floats(52, 2) * 4 == 151904 and R.stream_lds_floats(48, 2) * 4 == 147808
     for lq in R.STREAM_LQ:
         for nl in (1, 2):
-            assert R.stream_lds_floats(lq, nl) * 4 <= R.LDS_BOUND, (lq, nl)   # the streamed step never falls to the tile kernel for LDS
+            assert R.stream_lds_floats(lq, nl) * 4 <= R.LDS_BOUND, (lq, nl)   # what the source's static_assert over the streamed list says
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -68,12 +70,10 @@ def test_every_reachable_instance_is_listed_exactly_once():
     rows, unreachable = R.census()
     inst_rows = [r for r in rows if r.why == "instance"]
     built = R.built_instances()
-    assert len(built) == len(set(built)) == 52
+    assert len(built) == len(set(built)) == 41
+    assert unreachable == ()                                                    # every built instance has a smallest real shape
     listed = [r.inst for r in inst_rows]
-    assert len(listed) == len(set(listed))
-    assert set(listed) | {i for i, _ in unreachable} == set(built)
-    assert not set(listed) & {i for i, _ in unreachable}
-    assert all(why for _, why in unreachable), unreachable
+    assert len(listed) == len(set(listed)) and set(listed) == set(built)
     assert len({r.id for r in rows}) == len(rows)                               # ids are test ids: unique
     for r in rows:
         s = r.shape
@@ -89,12 +89,10 @@ def test_every_reachable_instance_is_listed_exactly_once():
     print("\n" + R.table_text())
 
 
-def test_unreachable_instances_are_unreachable_for_every_feature_count():
-    """The reasons of the census, checked over every (F, C, nl, switches), real shape or not."""
-    unreachable = {i for i, _ in R.census()[1]}
-    assert unreachable == ({("stream", 52, 2, 0, a) for a in R.ACTS} | {("tile", lq, nl, 0, "sine") for lq in R.TILE_LQ for nl in (1, 2)} |
-                           {("tile", 64, 3, 0, "sine")})
-    # <52, 2, ., 0>: LQ 52 is Fe 193..208, and all of them have thirteen strips
+def test_the_instances_reached_over_every_feature_count_are_exactly_the_built_ones():
+    """Every (F, C, nl, switches), real shape or not: each steps on a built instance or on the generic kernels (R.instance
+    asserts the first), and each built instance is reached -- the lists name nothing that cannot run."""
+    # no <52, 2, ., 0>: LQ 52 is Fe 193..208, and all of them have thirteen strips
     assert {(fe + 15) // 16 for fe in range(4 * 48 + 1, 4 * 52 + 1)} == {13}
     seen = set()
     for F in range(1, 420):
@@ -107,8 +105,32 @@ def test_unreachable_instances_are_unreachable_for_every_feature_count():
                         for alone in (False, True):
                             for B in (1, 2):
                                 seen.add(R.instance(*key, nl, act, alone=alone, count=1, B=B))
-    assert not seen & unreachable
-    assert seen - {R.GENERIC} == set(R.built_instances()) - unreachable
+    assert seen - {R.GENERIC} == set(R.built_instances())
+
+
+def _tile_plan_before_the_lists(F, C):
+    """The tile kernel's rule at nl = 3 as make_train_plan stated it while LQ 64 was on its list -> (LQ, NT0) or None."""
+    RP = (F + C + 3) // 4 * 4
+    LQ = next((lq for lq in (16, 32, 52, 64) if F <= 4 * lq and RP <= 4 * lq + 4), 0)
+    NT0 = (F + 15) // 16
+    if not LQ or 16 * NT0 > 4 * LQ + 4 or R.tile_lds_floats(LQ, NT0, 3) * 4 > R.LDS_BOUND:
+        return None
+    return LQ, NT0
+
+
+def test_tile_list_without_lq64_refuses_nothing_it_took():
+    """nl = 3, every F <= 256 and C <= 16: the plan never selects LQ 64 and plans exactly what the four-LQ rule planned.  The
+    tile kernel's LDS map at LQ 64 is (36,464 + 576 NT0) floats against 40,960: NT0 <= 7, F <= 112, and no such F needs LQ 64."""
+    assert R.tile_lds_floats(64, 0, 3) == 36464 and R.tile_lds_floats(64, 1, 3) - R.tile_lds_floats(64, 0, 3) == 576
+    planned = 0
+    for F in range(1, 257):
+        for C in range(1, 17):
+            p = R.plan(True, False, 0, C, 0, F, 3, "sine")
+            was = _tile_plan_before_the_lists(F, C)
+            assert (None if p is None else (p["LQ"], p["NT0"])) == was, (F, C, p, was)
+            assert p is None or (p["kind"] == "tile" and p["LQ"] in R.TILE_LQ and p["LQ"] != 64)
+            planned += p is not None
+    assert planned > 0 and R.plan(True, False, 0, 1, 0, 160, 3, "sine") and not R.plan(True, False, 0, 1, 0, 161, 3, "sine")
 
 
 def test_plan_restatement_agrees_with_the_library():

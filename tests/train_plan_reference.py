@@ -1,14 +1,14 @@
-"""Which template instance of the fused bc = 64 training step runs a shape: a plain Python restatement of make_train_plan,
-the dispatch_* functions and the split rules of csrc/train_mfma.hip (with stream_lds of csrc/train_stream.inc for the LDS
-bound), the constants of those sources read out of their text, and the census of instances the GPU test
-tests/test_gpu_train_instances.py steps one by one.
+"""Which template instance of the fused bc = 64 training step runs a shape: a plain Python restatement of make_train_plan and
+dispatch_train of csrc/train_mfma.hip (with stream_lds of csrc/train_stream.inc for the LDS bound), the three instance lists and
+the constants of that source read out of its text, and the census of instances the GPU test tests/test_gpu_train_instances.py
+steps one by one.
 
 A plain module: no fixture, no marker, no device.  tests/test_train_plan_host.py holds it to the source text and, where the
 library tells (lbdrn_train_step_features, lbdrn_train_group_size), to the library.
 
 An instance is (kernel, LQ, NL, NT0C, ACT): kernel "stream" (k_train_stream<LQ, NL, PD, NT0C, ACT>), "split"
-(k_train_split<LQ, NT0C, ACT>, NL = 2) or "tile" (k_train_mfma<LQ, NL> behind launch_train, Sine, NT0C = 0); NT0C = 0 is the
-generic weight-gradient loop.  "generic": the shape has no fused bc = 64 step."""
+(k_train_split<LQ, NT0C, ACT>, NL = 2) or "tile" (k_train_mfma<LQ, NL>, Sine, NT0C = 0); NT0C = 0 is the generic weight-gradient
+loop.  "generic": the shape has no fused bc = 64 step."""
 import functools
 import os
 import re
@@ -22,13 +22,16 @@ TRAIN_SOURCE = os.path.join(CSRC, "train_mfma.hip")
 # ---------------------------------------------------------------------------------------------------------------------
 # the intended values (tests/test_train_plan_host.py asserts that the source states the same)
 
-STREAM_LQ = (16, 24, 32, 48, 52, 64)        # layer-0 quarter lengths of the streamed step, tried in this order
-TILE_LQ = (16, 32, 52, 64)                  # ... of the nl = 3 tile kernel
+STREAM = ((16, 1, 0), (16, 2, 0), (24, 1, 0), (24, 2, 0), (24, 2, 6), (32, 1, 0), (32, 2, 0), (48, 1, 0), (48, 2, 0), (48, 2, 12),
+          (52, 1, 0), (52, 2, 13), (64, 1, 0), (64, 2, 0), (64, 2, 16))   # (LQ, NL, NT0C) of k_train_stream, ascending LQ
+SPLIT = ((24, 6), (48, 12), (64, 16), (96, 24))                 # (LQ, NT0C) of k_train_split
+TILE = ((16, 3), (32, 3), (52, 3))                              # (LQ, NL) of the tile kernel
+STREAM_LQ = tuple(sorted({lq for lq, nl, c in STREAM}))         # layer-0 quarter lengths of the streamed step
+TILE_LQ = tuple(lq for lq, nl in TILE)                          # ... of the nl = 3 tile kernel
+STRAIGHT = tuple((lq, c) for lq, nl, c in STREAM if c)          # (LQ, NT0) with a straight-line weight-gradient schedule
 SPLIT_WIDE_LQ = 96                          # 256 < Fe <= 384 at nl = 2: k_train_split only
 MAX_GROUP = 4                               # fits per launch (blockIdx.y)
 LDS_BOUND = 160 * 1024                      # bytes of LDS a workgroup may ask for
-STRAIGHT = ((24, 6), (48, 12), (52, 13), (64, 16))              # (LQ, NT0) with a straight-line weight-gradient schedule
-SPLIT = ((24, 6), (48, 12), (64, 16), (96, 24))                 # (LQ, NT0) that k_train_split is built for
 MAX_C, BC = 16, 64
 ACTS = ("sine", "relu")
 
@@ -36,44 +39,25 @@ GENERIC = "generic"
 
 
 def source_constants(text=None):
-    """The same constants as csrc/train_mfma.hip states them."""
+    """The same lists and constants as csrc/train_mfma.hip states them."""
     if text is None:
         with open(TRAIN_SOURCE) as f:
             text = f.read()
     k = {}
-    lists = re.findall(r"for \(int lq : \{([\d, ]+)\}\)", text)
-    assert len(lists) == 2, lists                           # make_train_plan: the streamed step's first, the tile kernel's second
-    k["STREAM_LQ"], k["TILE_LQ"] = (tuple(int(x) for x in l.split(",")) for l in lists)
+    for name in ("STREAM", "SPLIT", "TILE"):                # one X-macro list each: #define NAME_INSTANCES(X) X(..) X(..) ..
+        body, = re.findall(r"#define %s_INSTANCES\(X\)((?:[ \\\n]*X\([\d, ]+\))+)\n" % name, text)
+        k[name] = tuple(tuple(int(x) for x in row.split(",")) for row in re.findall(r"\(([\d, ]+)\)", body))
     for name in ("SPLIT_WIDE_LQ", "MAX_GROUP"):
         found = re.findall(r"constexpr int %s = (\d+);" % name, text)
         assert len(found) == 1, (name, found)
         k[name] = int(found[0])
-    bounds = re.findall(r"> (\d+) \* 1024\)", text)         # the streamed step's bound and the tile kernel's
+    bounds = re.findall(r"\* 4 [<>]=? (\d+) \* 1024", text)      # the static_assert over the streamed list and the tile kernel's check
     assert len(bounds) == 2 and len(set(bounds)) == 1, bounds
     k["LDS_BOUND"] = int(bounds[0]) * 1024
-    body = text[text.index("static int dispatch_stream("):text.index("static bool split_available(")]
-    inst = [(int(a), int(b), int(c)) for a, b, c in re.findall(r"launch_stream<(\d+), (\d), (\d+)>", body)]
-    k["STREAM_INSTANCES"] = tuple(sorted(inst))
-    guards = {(int(lq), int(nt)) for lq, nt in re.findall(r"case (\d+):\s+if \(!one && A\.p\.NT0 == (\d+)\)", body)}
-    dflt = re.findall(r"default:\s+if \(!one && A\.p\.NT0 == (\d+)\) return launch_stream<(\d+), 2, (\d+)>", body)
-    assert len(dflt) == 1 and dflt[0][0] == dflt[0][2], dflt
-    guards.add((int(dflt[0][1]), int(dflt[0][0])))
-    k["STRAIGHT"] = tuple(sorted((lq, c) for lq, nl, c in inst if c))
-    assert set(k["STRAIGHT"]) == guards, (k["STRAIGHT"], guards)      # each schedule sits behind the NT0 it was written for
-    assert all(nl == 2 for lq, nl, c in inst if c)
-    body = text[text.index("static bool split_available("):text.index("static int dispatch_train(")]
-    avail = {(int(a), int(b)) for a, b in re.findall(r"p\.LQ == (\d+) && p\.NT0 == (\d+)", body)}
-    assert "p.LQ == SPLIT_WIDE_LQ && p.NT0 == SPLIT_WIDE_LQ / 4" in body
-    assert "launch_split<SPLIT_WIDE_LQ, SPLIT_WIDE_LQ / 4>" in body
-    avail.add((k["SPLIT_WIDE_LQ"], k["SPLIT_WIDE_LQ"] // 4))
-    built = {(int(a), int(b)) for a, b in re.findall(r"launch_split<(\d+), (\d+)>", body)}
-    built.add((k["SPLIT_WIDE_LQ"], k["SPLIT_WIDE_LQ"] // 4))
-    assert avail == built, (avail, built)                   # split_available names exactly what dispatch_split launches
-    k["SPLIT"] = tuple(sorted(built))
-    body = text[text.index("static int dispatch_train("):text.index("int mfma_train_prepare(")]
-    tile = [int(x) for x in re.findall(r"dispatch_nl<(\d+)>", body)]
-    k["TILE_DISPATCH"] = tuple(sorted(tile))
-    assert "split && (B >= 2 || split_only(A.p))" in text   # the B >= 2 rule
+    # how the lists are read: the schedule of exactly NT0 strips where there is one, k_train_split by (LQ, NT0), the B >= 2 rule
+    assert "if (lq == LQ && nl == NL && nt0 == NT0C) return NT0C;" in text
+    assert "p.wave == STEP_STREAM && net.nl == 2 && split_nt0c(p.LQ) == p.NT0" in text
+    assert "split && (B >= 2 || split_only(A.p))" in text
     assert "(alone && count == 1 && split_available(A.p, net)) || split_only(A.p)" in text
     return k
 
@@ -126,22 +110,18 @@ def plan(use_colors, relative, P, C, D, F, nl, act):
         return None
     if act == "relu" and nl > 2:
         return None
-    if nl <= 2:
+    if nl <= 2:   # the streamed step or k_train_split, or nothing
         Fe = centre_skipping_fe(use_colors, relative, P, C, D, F)
-        LQ = next((lq for lq in STREAM_LQ if Fe <= 4 * lq), 0)
+        LQ = next((lq for lq, n, c in STREAM if n == nl and Fe <= 4 * lq), 0)
         if not LQ and nl == 2 and Fe <= 4 * SPLIT_WIDE_LQ:
             LQ = SPLIT_WIDE_LQ
-        if LQ and (LQ == SPLIT_WIDE_LQ or stream_lds_floats(LQ, nl) * 4 <= LDS_BOUND):
-            NT0 = SPLIT_WIDE_LQ // 4 if LQ == SPLIT_WIDE_LQ else (Fe + 15) // 16
-            return dict(kind="stream", LQ=LQ, Fe=Fe, NT0=NT0)
-    if act != "sine":
-        return None
+        if not LQ:
+            return None
+        return dict(kind="stream", LQ=LQ, Fe=Fe, NT0=dict(SPLIT)[LQ] if LQ == SPLIT_WIDE_LQ else (Fe + 15) // 16)
     RP = (F + C + 3) // 4 * 4
-    LQ = next((lq for lq in TILE_LQ if F <= 4 * lq and RP <= 4 * lq + 4), 0)
-    if not LQ:
-        return None
+    LQ = next((lq for lq, n in TILE if n == nl and F <= 4 * lq and RP <= 4 * lq + 4), 0)
     NT0 = (F + 15) // 16
-    if 16 * NT0 > 4 * LQ + 4 or tile_lds_floats(LQ, NT0, nl) * 4 > LDS_BOUND:
+    if not LQ or tile_lds_floats(LQ, NT0, nl) * 4 > LDS_BOUND:
         return None
     return dict(kind="tile", LQ=LQ, Fe=F, NT0=NT0)
 
@@ -161,26 +141,27 @@ def instance(use_colors, relative, P, C, D, F, nl, act, alone=False, count=1, B=
         return GENERIC
     assert 1 <= count <= MAX_GROUP and (count == 1 or takes_groups(p)) and B >= 1
     if p["kind"] == "tile":
-        return ("tile", p["LQ"], nl, 0, "sine")
-    split_only = p["LQ"] == SPLIT_WIDE_LQ
-    split = (alone and count == 1 and split_available(p, nl)) or split_only
-    if split and (B >= 2 or split_only):
-        return ("split", p["LQ"], 2, p["NT0"], act)
-    nt0c = p["NT0"] if nl == 2 and (p["LQ"], p["NT0"]) in STRAIGHT else 0
-    return ("stream", p["LQ"], nl, nt0c, act)
+        inst = ("tile", p["LQ"], nl, 0, "sine")
+    else:
+        split_only = p["LQ"] == SPLIT_WIDE_LQ
+        split = (alone and count == 1 and split_available(p, nl)) or split_only
+        if split and (B >= 2 or split_only):
+            inst = ("split", p["LQ"], 2, p["NT0"], act)
+        else:
+            inst = ("stream", p["LQ"], nl, p["NT0"] if (p["LQ"], nl, p["NT0"]) in STREAM else 0, act)
+    assert inst in built_instances(), inst      # dispatch_train refuses what no list names: a plan never gets there
+    return inst
 
 
+@functools.lru_cache(maxsize=None)
 def built_instances():
-    """Every instance the dispatch functions can name (what the library is compiled with)."""
+    """Every instance the three lists name (what the library is compiled with): the loops, the straight-line schedules and
+    k_train_split per activation, then the tile kernel's."""
     out = []
     for act in ACTS:
-        for lq in STREAM_LQ:
-            for nl in (1, 2):
-                out.append(("stream", lq, nl, 0, act))
-        out += [("stream", lq, 2, nt, act) for lq, nt in STRAIGHT]
-        out += [("split", lq, 2, nt, act) for lq, nt in SPLIT]
-    out += [("tile", lq, nl, 0, "sine") for lq in TILE_LQ for nl in (1, 2, 3)]
-    return out
+        out += [("stream", lq, nl, c, act) for lq, nl, c in sorted(STREAM, key=lambda r: r[2] > 0)]
+        out += [("split", lq, 2, c, act) for lq, c in SPLIT]
+    return tuple(out + [("tile", lq, nl, 0, "sine") for lq, nl in TILE])
 
 
 def instance_id(inst, Fe):
@@ -299,28 +280,15 @@ def _smallest(inst):
     return None
 
 
-def _why_unreachable(inst):
-    kernel, lq, nl, nt0c, act = inst
-    if kernel == "stream" and (lq, nl, nt0c) == (52, 2, 0):
-        return "every Fe in 193..208 has NT0 = 13: the straight-line schedule <52,2,.,13> takes them all"
-    if kernel == "tile" and nl < 3:
-        return ("nl <= 2 steps on k_train_stream whenever Fe <= 256 (its LDS map stays under the bound at every LQ), and a shape "
-                "past that has F > 256, which the tile kernel does not take either")
-    if inst == ("tile", 64, 3, 0, "sine"):
-        return ("LQ 64 means F > 208 or F + C > 212, so fourteen strips or thirteen: the tile kernel's LDS map at nl = 3 passes "
-                "160 KB from eleven strips on, and make_train_plan refuses the shape (it steps on the generic kernels)")
-    return None
-
-
 @functools.lru_cache(maxsize=None)
 def census():
-    """-> (rows, unreachable): rows = one Row per reachable built instance (its smallest real shape) followed by the rows
-    that the class boundaries and the multiple-of-16 rule add; unreachable = [(instance, reason)]."""
+    """-> (rows, unreachable): rows = one Row per built instance (its smallest real shape) followed by the rows that the class
+    boundaries and the multiple-of-16 rule add; unreachable = the built instances no real shape selects (there are none)."""
     rows, unreachable, seen = [], [], set()
     for inst in built_instances():
         r = _smallest(inst)
         if r is None:
-            unreachable.append((inst, _why_unreachable(inst)))
+            unreachable.append(inst)
         else:
             rows.append(r)
             seen.add((r.shape.key(), r.alone))
@@ -346,12 +314,10 @@ def census():
 
 
 def table_text():
-    rows, unreachable = census()
+    rows, _ = census()
     lines = ["| instance | smallest shape | F | Fe | NT0 | why |", "|---|---|---|---|---|---|"]
     for r in rows:
         lines.append(f"| `{r.id}`{' (alone)' if r.alone else ''} | {r.shape!r} | {r.shape.F} | {r.Fe} | {r.NT0} | {r.why} |")
-    for inst, why in unreachable:
-        lines.append(f"| `{instance_id(inst, '-')}` | unreachable | | | | {why} |")
     return "\n".join(lines)
 
 
