@@ -18,7 +18,6 @@
 //    conflict-free ds_read_b64; the D-ring of normalised MSB values is staged per 16x64 tile in
 //    channel-planar LDS (conflict-free for 32 consecutive pixels) with reflect padding applied.
 //  * 8 waves per CU (2 per SIMD): one wave's sin() VALU work overlaps the other's MFMAs.
-#include <atomic>
 #include <cstdlib>
 
 #include "common.hpp"
@@ -43,6 +42,50 @@ __host__ __device__ inline int tile_row_to_neuron(int i)
 }
 // accumulator register r of lane-half h is tile row:
 __host__ __device__ inline int acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+enum ApplyMode { MODE_DECODE = 0, MODE_EVAL = 1, MODE_EVAL_FAST = 2,   // _FAST: the evaluation pass in the tolerance arithmetic (lbdrn_math.hpp)
+                 MODE_EVAL_X16 = 3 };   // _FAST with the colour features of layer 0 on the f16 matrix pipe, exact operands (opt-in)
+__host__ __device__ constexpr bool mode_fast(int mode) { return mode == MODE_EVAL_FAST || mode == MODE_EVAL_X16; }
+
+// ---- the instances of the fused apply pass: every kernel that is compiled, each list stated once.  The planners, the mode a
+// request is served in and the two dispatch functions all come from these lists.
+//
+// k_apply_mfma<NT, MODE, RELU> (NT = bc / 32 hidden tiles, weights resident in LDS), both activations.  No (4, MODE_EVAL_FAST): at
+// bc = 128 the tolerance arithmetic's extra operands spill at two waves per SIMD (88 registers, 356 B of scratch when it was
+// instantiated), and the canonical pass IS within the 1e-6 the flag promises.  No (4, MODE_EVAL_X16): ApplyPlan::pair stops at NT = 2.
+#define APPLY_INSTANCES(X) \
+    X(1, MODE_DECODE)    X(2, MODE_DECODE)    X(4, MODE_DECODE) \
+    X(1, MODE_EVAL)      X(2, MODE_EVAL)      X(4, MODE_EVAL)   \
+    X(1, MODE_EVAL_FAST) X(2, MODE_EVAL_FAST)                   \
+    X(1, MODE_EVAL_X16)  X(2, MODE_EVAL_X16)
+// k_apply_wide<NT, NL, MODE> (apply_wide.inc: NT = bc / 16 unit tiles, weights streamed; the Sine network), each row in MODE_DECODE,
+// MODE_EVAL and MODE_EVAL_FAST: the streaming kernel has no exact-operand layer 0.
+#define WAPPLY_INSTANCES(X) X(8, 1) X(8, 2) X(16, 1) X(16, 2)
+
+// What the rest reads off the lists: whether a row names (nt, mode) / (nt, nl); a negative mode or nl stands for any.
+#define X(NT, MODE) if (nt == NT && (mode < 0 || mode == MODE)) return true;
+constexpr bool apply_row(int nt, int mode = -1) { APPLY_INSTANCES(X) return false; }
+#undef X
+#define X(NT, NL) if (nt == NT && (nl < 0 || nl == NL)) return true;
+constexpr bool wapply_row(int nt, int nl = -1) { WAPPLY_INSTANCES(X) return false; }
+#undef X
+// The mode of the instance that serves a requested mode on nt tiles (x16: the plan has ApplyPlan::x16; never on the wide kernel):
+// the exact-operand pass where the plan and a row have it, else the fast pass; the fast pass where a row has it, else the canonical one.
+constexpr int serving_mode(int mode, int nt, bool x16)
+{
+    if (mode == MODE_EVAL_X16 && !(x16 && apply_row(nt, MODE_EVAL_X16))) mode = MODE_EVAL_FAST;
+    if (mode == MODE_EVAL_FAST && !(apply_row(nt, MODE_EVAL_FAST) || wapply_row(nt))) mode = MODE_EVAL;
+    return mode;
+}
+// requested mode x {NT 1 / 2, NT 4, wide} x {plan without / with x16}: the whole domain
+#define SERVES(mode, x16, nt12, nt4, wide)                                                                                          \
+    static_assert(serving_mode(mode, 1, x16) == nt12 && serving_mode(mode, 2, x16) == nt12 && serving_mode(mode, 4, x16) == nt4 && \
+                  serving_mode(mode, 8, x16) == wide && serving_mode(mode, 16, x16) == wide, #mode);
+SERVES(MODE_DECODE, false, MODE_DECODE, MODE_DECODE, MODE_DECODE)          SERVES(MODE_DECODE, true, MODE_DECODE, MODE_DECODE, MODE_DECODE)
+SERVES(MODE_EVAL, false, MODE_EVAL, MODE_EVAL, MODE_EVAL)                  SERVES(MODE_EVAL, true, MODE_EVAL, MODE_EVAL, MODE_EVAL)
+SERVES(MODE_EVAL_FAST, false, MODE_EVAL_FAST, MODE_EVAL, MODE_EVAL_FAST)   SERVES(MODE_EVAL_FAST, true, MODE_EVAL_FAST, MODE_EVAL, MODE_EVAL_FAST)
+SERVES(MODE_EVAL_X16, false, MODE_EVAL_FAST, MODE_EVAL, MODE_EVAL_FAST)    SERVES(MODE_EVAL_X16, true, MODE_EVAL_X16, MODE_EVAL, MODE_EVAL_FAST)
+#undef SERVES
 
 struct ApplyPlan {
     int NT;          // hidden tiles = bc/32
@@ -73,7 +116,7 @@ static bool make_plan(const lbdrn_geom& g, const lbdrn_net& net, ApplyPlan* p, b
     // hidden activation: Sine(30) (LBDRNmodel.py:37) or nn.ReLU (the alternative of encode.py:75 / decode.py:108): a template
     // parameter of k_apply_mfma
     if (net.act != LBDRN_ACT_SINE && net.act != LBDRN_ACT_RELU) return false;
-    if (net.bc % 32 != 0 || net.bc < 32 || net.bc > 128) return false;
+    if (net.bc % 32 != 0 || !apply_row(net.bc / 32)) return false;   // (bc = 96 would be NT = 3: no such kernel, the generic ones)
     if (net.C > 32 || net.nl < 1 || net.nl > 15) return false;
     ApplyPlan q;
     q.NT = net.bc / 32;
@@ -122,35 +165,7 @@ static bool make_plan(const lbdrn_geom& g, const lbdrn_net& net, ApplyPlan* p, b
     return true;
 }
 
-struct WApplyPlan;
-static bool wapply_supported(const lbdrn_geom& g, const lbdrn_net& net);
-static size_t wapply_workspace(const lbdrn_geom& g, const lbdrn_net& net);
-
-bool mfma_apply_supported(const lbdrn_geom& g, const lbdrn_net& net)
-{
-    ApplyPlan p;
-    return make_plan(g, net, &p) || wapply_supported(g, net);
-}
-
 constexpr int MFMA_PARTIALS = 1024;
-
-// the packed weights of the largest of a shape's plans | the SSE partials | one float: max |W_0| (x16)
-static size_t apply_pack_bytes(const lbdrn_geom& g, const lbdrn_net& net)
-{
-    ApplyPlan p{}, q{};
-    if (!make_plan(g, net, &p)) return 0;
-    lbdrn_geom gx = g;
-    gx.msb_max = 1;                     // (the workspace is sized before the image's maximum is known to the caller's struct)
-    const bool x = make_plan(gx, net, &q, true, true) && q.x16;
-    return align_up((size_t)std::max(p.pack_floats, x ? q.pack_floats : 0) * 4, 256);
-}
-
-size_t mfma_apply_workspace(const lbdrn_geom& g, const lbdrn_net& net)
-{
-    ApplyPlan p;
-    if (!make_plan(g, net, &p)) return wapply_workspace(g, net);
-    return apply_pack_bytes(g, net) + align_up(MFMA_PARTIALS * sizeof(double), 256) + 256;
-}
 
 // ------------------------------------------------------------------ weight packing
 
@@ -256,10 +271,6 @@ __global__ void __launch_bounds__(256)
 }
 
 // ------------------------------------------------------------------ the fused kernel
-
-enum ApplyMode { MODE_DECODE = 0, MODE_EVAL = 1, MODE_EVAL_FAST = 2,   // _FAST: the evaluation pass in the tolerance arithmetic (lbdrn_math.hpp)
-                 MODE_EVAL_X16 = 3 };   // _FAST with the colour features of layer 0 on the f16 matrix pipe, exact operands (opt-in)
-__host__ __device__ constexpr bool mode_fast(int mode) { return mode == MODE_EVAL_FAST || mode == MODE_EVAL_X16; }
 
 struct ApplyArgs {
     lbdrn_geom g;
@@ -720,45 +731,8 @@ __global__ void k_sum_partials_mfma(const double* __restrict__ partial, int n, d
     if (lane == 0) *dst = s;
 }
 
-template <int NT, int MODE, bool RELU>
-static int launch_apply_act(const ApplyArgs& A, int grid, hipStream_t s, bool whole_lds)
-{
-    // whole_lds (a fit's background evaluation pass): the workgroup asks for 125 of the CU's 128 LDS granules of 1,280
-    // bytes whatever it needs, so that the k_reduce_adam launches of the training chain beside it (4 granules) are
-    // placed on the CUs the chain's own training step has just left, not next to this pass's waves -- there they took
-    // 14.4 instead of 4.9 us (kernel trace of a fit alone, scripts/lone_timeline.py)
-    const size_t lds_bytes = std::max((size_t)A.p.lds_floats * 4, whole_lds ? (size_t)125 * 1280 : (size_t)0);
-    auto kern = k_apply_mfma<NT, MODE, RELU>;
-    // the kernel may use the whole 160 KB of a CU's LDS: told to the runtime once per device and kernel (a cache of an
-    // idempotent setting, not state a caller can observe)
-    static std::atomic<unsigned long long> configured{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(configured.load(std::memory_order_relaxed) & bit)) {
-        LBDRN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        configured.fetch_or(bit, std::memory_order_relaxed);
-    }
-    kern<<<grid, APPLY_THREADS, lds_bytes, s>>>(A);
-    LBDRN_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int NT, int MODE>
-static int launch_apply(const ApplyArgs& A, int grid, hipStream_t s, bool whole_lds = false)
-{
-    return A.net.act == LBDRN_ACT_RELU ? launch_apply_act<NT, MODE, true>(A, grid, s, whole_lds)
-                                       : launch_apply_act<NT, MODE, false>(A, grid, s, whole_lds);
-}
-
 #include "apply_wide.inc"
 
-static bool wapply_supported(const lbdrn_geom& g, const lbdrn_net& net)
-{
-    WApplyPlan p;
-    return make_wapply_plan(g, net, &p);
-}
 static size_t wapply_workspace(const lbdrn_geom& g, const lbdrn_net& net)
 {
     WApplyPlan p;
@@ -766,96 +740,168 @@ static size_t wapply_workspace(const lbdrn_geom& g, const lbdrn_net& net)
     return align_up((size_t)p.pack_floats * 4, 256) + align_up(MFMA_PARTIALS * sizeof(double), 256);
 }
 
-template <int NT, int NL, int MODE>
-static int launch_wapply(const WApplyArgs& A, int grid, hipStream_t s, bool whole_lds)
+bool mfma_apply_supported(const lbdrn_geom& g, const lbdrn_net& net)
 {
-    // whole_lds: a fit's background pass claims its CU's LDS like k_apply_mfma's does (launch_apply), so that the reduce
-    // launches of the training chain beside it land on the CUs the chain's own step has just left
+    ApplyPlan p;
+    WApplyPlan w;
+    return make_plan(g, net, &p) || make_wapply_plan(g, net, &w);
+}
+
+// the packed weights of the largest of a shape's plans | the SSE partials | one float: max |W_0| (x16)
+static size_t apply_pack_bytes(const lbdrn_geom& g, const lbdrn_net& net)
+{
+    ApplyPlan p{}, q{};
+    if (!make_plan(g, net, &p)) return 0;
+    lbdrn_geom gx = g;
+    gx.msb_max = 1;                     // (the workspace is sized before the image's maximum is known to the caller's struct)
+    const bool x = make_plan(gx, net, &q, true, true) && q.x16;
+    return align_up((size_t)std::max(p.pack_floats, x ? q.pack_floats : 0) * 4, 256);
+}
+
+size_t mfma_apply_workspace(const lbdrn_geom& g, const lbdrn_net& net)
+{
+    ApplyPlan p;
+    if (!make_plan(g, net, &p)) return wapply_workspace(g, net);
+    return apply_pack_bytes(g, net) + align_up(MFMA_PARTIALS * sizeof(double), 256) + 256;
+}
+
+// Launch either kernel.  ALWAYS_160K: the kernel may use the whole 160 KB of a CU's LDS (k_apply_mfma; k_apply_wide's own map
+// stays under the 64 KB no kernel has to ask for).  whole_lds (a fit's background evaluation pass): the workgroup asks for 125 of
+// the CU's 128 LDS granules of 1,280 bytes whatever it needs, so that the k_reduce_adam launches of the training chain beside it
+// (4 granules) are placed on the CUs the chain's own training step has just left, not next to this pass's waves -- there they
+// took 14.4 instead of 4.9 us (kernel trace of a fit alone, scripts/lone_timeline.py; bc = 256, one tile alone: 569.5 -> 558.5 ms)
+template <auto KERN, int THREADS, bool ALWAYS_160K, class Args>
+static int launch_pass(const Args& A, int grid, hipStream_t s, bool whole_lds)
+{
     const size_t lds_bytes = std::max((size_t)A.p.lds_floats * 4, whole_lds ? (size_t)125 * 1280 : (size_t)0);
-    auto kern = k_apply_wide<NT, NL, MODE>;
-    if (whole_lds) {
-        static std::atomic<unsigned long long> configured{0};
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(configured.load(std::memory_order_relaxed) & bit)) {
-            LBDRN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            configured.fetch_or(bit, std::memory_order_relaxed);
-        }
-    }
-    kern<<<grid, WA_THREADS, lds_bytes, s>>>(A);
+    static std::atomic<unsigned long long> configured{0};   // (one per kernel instance)
+    if (ALWAYS_160K || whole_lds)
+        if (int rc = configure_lds_once(KERN, 160 * 1024, configured)) return rc;
+    KERN<<<grid, THREADS, lds_bytes, s>>>(A);
     LBDRN_LAUNCH_CHECK();
     return 0;
 }
 
-template <int MODE>
-static int dispatch_wapply(const WApplyArgs& A, int grid, hipStream_t s, bool whole_lds)
+// The one place a kernel of each list is named for launching.  A (NT, mode) or (NT, nl) that no row names is one the planners do
+// not plan and serving_mode does not answer: it is refused, never run on some other instance.
+static int dispatch_apply(const ApplyArgs& A, int mode, int grid, hipStream_t s, bool whole_lds)
 {
-    const bool one = A.net.nl == 1;
-    if (A.p.NT == 8) return one ? launch_wapply<8, 1, MODE>(A, grid, s, whole_lds) : launch_wapply<8, 2, MODE>(A, grid, s, whole_lds);
-    return one ? launch_wapply<16, 1, MODE>(A, grid, s, whole_lds) : launch_wapply<16, 2, MODE>(A, grid, s, whole_lds);
+    const bool relu = A.net.act == LBDRN_ACT_RELU;
+#define X(nt, m)                                                                                                       \
+    if (A.p.NT == nt && mode == m)                                                                                     \
+        return relu ? launch_pass<k_apply_mfma<nt, m, true>, APPLY_THREADS, true>(A, grid, s, whole_lds)               \
+                    : launch_pass<k_apply_mfma<nt, m, false>, APPLY_THREADS, true>(A, grid, s, whole_lds);
+    APPLY_INSTANCES(X)
+#undef X
+    set_error("no fused apply pass is built for NT = %d, mode %d", A.p.NT, mode);
+    return LBDRN_E_UNSUPPORTED;
 }
 
-static int run_wapply(const lbdrn_geom& g, const lbdrn_net& net, int mode, const uint16_t* img,
-                      const uint16_t* msb, const float* params, uint16_t* out, float* y_out,
-                      double* sse, void* ws, size_t ws_bytes, bool background, hipStream_t s)
+static int dispatch_wapply(const WApplyArgs& A, int mode, int grid, hipStream_t s, bool whole_lds)
 {
-    WApplyArgs A;
-    if (mode == MODE_EVAL_X16) mode = MODE_EVAL_FAST;     // (the streaming kernel has no exact-operand layer 0)
-    if (!make_wapply_plan(g, net, &A.p, mode == MODE_EVAL_FAST)) {
-        set_error("shape not supported by the MFMA apply kernels");
-        return LBDRN_E_UNSUPPORTED;
-    }
-    if (!ws || ws_bytes < wapply_workspace(g, net)) {
-        set_error("apply workspace too small: %zu < %zu", ws_bytes, wapply_workspace(g, net));
-        return LBDRN_E_WORKSPACE;
-    }
-    float* packed = (float*)ws;
-    double* partial = (double*)((char*)ws + align_up((size_t)A.p.pack_floats * 4, 256));
-    k_pack_apply_wide<<<(A.p.pack_floats + 255) / 256, 256, 0, s>>>(params, net, A.p, 2 * g.P, packed);
-    LBDRN_LAUNCH_CHECK();
-    A.g = g; A.net = net; A.packed = packed; A.msb = msb; A.img = img; A.out = out; A.y_out = y_out;
-    A.partial = partial;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    A.nvirt = std::min(std::min(A.p.tiles_x * A.p.tiles_y, cus), MFMA_PARTIALS);
-    const int grid = background ? std::max(1, A.nvirt / 2) : A.nvirt;
-    A.stamps = nullptr;
+#define LAUNCH(nt, n, m) if (mode == m) return launch_pass<k_apply_wide<nt, n, m>, WA_THREADS, false>(A, grid, s, whole_lds);
+#define X(nt, n) if (A.p.NT == nt && A.net.nl == n) { LAUNCH(nt, n, MODE_DECODE) LAUNCH(nt, n, MODE_EVAL) LAUNCH(nt, n, MODE_EVAL_FAST) }
+    WAPPLY_INSTANCES(X)
+#undef X
+#undef LAUNCH
+    set_error("no streamed apply pass is built for NT = %d, nl = %d, mode %d", A.p.NT, A.net.nl, mode);
+    return LBDRN_E_UNSUPPORTED;
+}
+
+struct ApplyCall {   // what an entry point hands the driver
+    const lbdrn_geom& g;
+    const lbdrn_net& net;
+    const uint16_t *img, *msb;   // img: EVAL only
+    const float* params;
+    uint16_t* out;   // DECODE
+    float* y_out;    // DECODE, optional
+    double* sse;     // EVAL
+    void* ws;
+    size_t ws_bytes;
+    bool background;
+    hipStream_t s;
+};
+
+static int workspace_holds(const ApplyCall& c, size_t need)
+{
+    if (c.ws && c.ws_bytes >= need) return 0;
+    set_error("apply workspace too small: %zu < %zu", c.ws_bytes, need);
+    return LBDRN_E_WORKSPACE;
+}
+
+// diagnostic build: wave 0's cycle sums of every workgroup, read back and printed per pass
+template <class Args>
+static int report_stamps(const Args& A, int grid, hipStream_t s)
+{
 #ifdef LBDRN_APPLY_STAMPS
-    static unsigned long long* wstamp_buf = nullptr;
-    if (!wstamp_buf) LBDRN_HIP_TRY(hipMalloc(&wstamp_buf, 1024 * 8 * sizeof(unsigned long long)));
-    A.stamps = wstamp_buf;
-#endif
-    const bool claim = background;   // (bc = 256, one tile alone: 569.5 -> 558.5 ms)
-    int rc = mode == MODE_DECODE ? dispatch_wapply<MODE_DECODE>(A, grid, s, false)
-           : mode == MODE_EVAL_FAST ? dispatch_wapply<MODE_EVAL_FAST>(A, grid, s, claim) : dispatch_wapply<MODE_EVAL>(A, grid, s, claim);
-    if (rc) return rc;
-    if (mode != MODE_DECODE) {
-        k_sum_partials_mfma<<<1, 64, 0, s>>>(partial, A.nvirt, sse);
-        LBDRN_LAUNCH_CHECK();
-    }
-#ifdef LBDRN_APPLY_STAMPS
-    {
-        LBDRN_HIP_TRY(hipStreamSynchronize(s));
-        unsigned long long h[1024 * 8];
-        LBDRN_HIP_TRY(hipMemcpy(h, A.stamps, (size_t)grid * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double sum[8] = {};
-        for (int b = 0; b < grid; ++b) for (int k = 0; k < 8; ++k) sum[k] += (double)h[b * 8 + k];
+    LBDRN_HIP_TRY(hipStreamSynchronize(s));
+    unsigned long long h[1024 * 8];
+    LBDRN_HIP_TRY(hipMemcpy(h, A.stamps, (size_t)grid * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    double sum[8] = {};
+    for (int b = 0; b < grid; ++b) for (int k = 0; k < 8; ++k) sum[k] += (double)h[b * 8 + k];
+    if constexpr (std::is_same<Args, WApplyArgs>::value) {
         const double segs = (double)A.p.tiles_x * A.p.tiles_y * A.p.TH * (TILE_W / 16) / 4 / grid;
         double rtmin = 1e30, rtmax = 0;
         for (int b = 0; b < grid; ++b) { rtmin = std::min(rtmin, (double)h[b * 8 + 6]); rtmax = std::max(rtmax, (double)h[b * 8 + 6]); }
         fprintf(stderr, "[lbdrn wide apply stamps] wave lifetime %.2f .. %.2f ms (mean %.2f); per wave: tiles-staging %.0f total; per 16-px segment: L0 %.0f sin %.0f L1 %.0f last %.0f epilogue %.0f\n",
                 rtmin / 1e5, rtmax / 1e5, sum[6] / grid / 1e5, sum[0] / grid, sum[1] / grid / segs, sum[2] / grid / segs, sum[3] / grid / segs, sum[4] / grid / segs, sum[5] / grid / segs);
+    } else {
+        const double blocks = (double)A.p.tiles_x * A.p.tiles_y * A.p.TH * (TILE_W / 32) / APPLY_WAVES / grid;
+        fprintf(stderr, "[lbdrn apply stamps] per wave: tiles-staging %.0f total; per 32-px block: L0 %.0f sin %.0f hidden %.0f last %.0f epilogue %.0f\n",
+                sum[0] / grid, sum[1] / grid / blocks, sum[2] / grid / blocks, sum[3] / grid / blocks, sum[4] / grid / blocks, sum[5] / grid / blocks);
     }
 #endif
     return 0;
 }
 
-static int run_apply(const lbdrn_geom& g, const lbdrn_net& net, int mode, const uint16_t* img,
-                     const uint16_t* msb, const float* params, uint16_t* out, float* y_out,
-                     double* sse, void* ws, size_t ws_bytes, bool background, hipStream_t s)
+// What a pass of either kernel does once its plan is made and its weights are packed: fill the args, size the launch, run the
+// instance that serves `mode`, sum the evaluation's partials.
+template <class Args>
+static int run_pass(Args& A, const ApplyCall& c, int mode, const float* packed, double* partial,
+                    int (*dispatch)(const Args&, int, int, hipStream_t, bool))
 {
+    A.g = c.g; A.net = c.net; A.packed = packed; A.msb = c.msb; A.img = c.img; A.out = c.out; A.y_out = c.y_out; A.partial = partial;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess)
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    A.nvirt = std::min(std::min(A.p.tiles_x * A.p.tiles_y, cus), MFMA_PARTIALS);
+    // a background pass (beside a training stream that holds the other half of the CUs) launches half as many
+    // workgroups, each walking two virtual ones
+    const int grid = c.background ? std::max(1, A.nvirt / 2) : A.nvirt;   // (a quarter / a sixth: 3 / 10 ms per tile slower)
+    A.stamps = nullptr;
+#ifdef LBDRN_APPLY_STAMPS
+    static unsigned long long* stamp_buf = nullptr;
+    if (!stamp_buf) LBDRN_HIP_TRY(hipMalloc(&stamp_buf, 1024 * 8 * sizeof(unsigned long long)));
+    A.stamps = stamp_buf;
+#endif
+    // evaluation claims the whole LDS exactly when it runs in the background; the decode pass never does
+    if (int rc = dispatch(A, mode, grid, c.s, c.background && mode != MODE_DECODE)) return rc;
+    if (mode != MODE_DECODE) {
+        k_sum_partials_mfma<<<1, 64, 0, c.s>>>(partial, A.nvirt, c.sse);
+        LBDRN_LAUNCH_CHECK();
+    }
+    return report_stamps(A, grid, c.s);
+}
+
+static int run_wapply(const ApplyCall& c, int mode)
+{
+    WApplyArgs A;
+    if (!make_wapply_plan(c.g, c.net, &A.p, mode_fast(mode))) {
+        set_error("shape not supported by the MFMA apply kernels");
+        return LBDRN_E_UNSUPPORTED;
+    }
+    if (int rc = workspace_holds(c, wapply_workspace(c.g, c.net))) return rc;
+    float* packed = (float*)c.ws;
+    double* partial = (double*)((char*)c.ws + align_up((size_t)A.p.pack_floats * 4, 256));
+    k_pack_apply_wide<<<(A.p.pack_floats + 255) / 256, 256, 0, c.s>>>(c.params, c.net, A.p, 2 * c.g.P, packed);
+    LBDRN_LAUNCH_CHECK();
+    return run_pass(A, c, serving_mode(mode, A.p.NT, false), packed, partial, dispatch_wapply);
+}
+
+static int run_apply(const ApplyCall& c, int mode)
+{
+    const lbdrn_geom& g = c.g;
+    const lbdrn_net& net = c.net;
     ApplyArgs A;
     if (mode == MODE_EVAL_X16) {   // (a hint: where the x16 weight pack does not fit in LDS, or fits only at a shorter tile than the fast
                                    //  plan's -- C = 8, D = 3, bc = 64 --, the pass is the fast one)
@@ -863,85 +909,34 @@ static int run_apply(const lbdrn_geom& g, const lbdrn_net& net, int mode, const 
         if (make_plan(g, net, &fp, true, false) && (!make_plan(g, net, &xp, true, true) || xp.TH < fp.TH)) mode = MODE_EVAL_FAST;
     }
     if (!make_plan(g, net, &A.p, mode_fast(mode), mode == MODE_EVAL_X16))   // too wide for LDS-resident weights: the streaming kernel (apply_wide.inc)
-        return run_wapply(g, net, mode, img, msb, params, out, y_out, sse, ws, ws_bytes, background, s);
-    if (mode == MODE_EVAL_X16 && !A.p.x16) mode = MODE_EVAL_FAST;    // (a hint: the shape or the image does not qualify, the pass is the fast one)
-    if (!ws || ws_bytes < mfma_apply_workspace(g, net)) {
-        set_error("apply workspace too small: %zu < %zu", ws_bytes, mfma_apply_workspace(g, net));
-        return LBDRN_E_WORKSPACE;
-    }
-    float* packed = (float*)ws;
+        return run_wapply(c, mode);
+    mode = serving_mode(mode, A.p.NT, A.p.x16);   // (x16 is a hint: where the shape or the image does not qualify, the pass is the fast one)
+    if (int rc = workspace_holds(c, mfma_apply_workspace(g, net))) return rc;
+    float* packed = (float*)c.ws;
     const size_t pack_bytes = apply_pack_bytes(g, net);
-    double* partial = (double*)((char*)ws + pack_bytes);
-    float* amax = (float*)((char*)ws + pack_bytes + align_up(MFMA_PARTIALS * sizeof(double), 256));
+    double* partial = (double*)((char*)c.ws + pack_bytes);
+    float* amax = (float*)((char*)c.ws + pack_bytes + align_up(MFMA_PARTIALS * sizeof(double), 256));
     if (A.p.x16) {
-        k_w0_absmax<<<1, 256, 0, s>>>(params, net.bc * net.F, amax);
+        k_w0_absmax<<<1, 256, 0, c.s>>>(c.params, net.bc * net.F, amax);
         LBDRN_LAUNCH_CHECK();
     }
-    k_pack_apply<<<(A.p.pack_floats + 255) / 256, 256, 0, s>>>(params, net, A.p, g.P, g.C, g.msb_max, amax, packed);
+    k_pack_apply<<<(A.p.pack_floats + 255) / 256, 256, 0, c.s>>>(c.params, net, A.p, g.P, g.C, g.msb_max, amax, packed);
     LBDRN_LAUNCH_CHECK();
-    A.g = g; A.net = net; A.packed = packed; A.msb = msb; A.img = img; A.out = out; A.y_out = y_out;
-    A.partial = partial;
-    A.stamps = nullptr;
-#ifdef LBDRN_APPLY_STAMPS
-    static unsigned long long* stamp_buf = nullptr;
-    if (!stamp_buf) LBDRN_HIP_TRY(hipMalloc(&stamp_buf, 1024 * 8 * sizeof(unsigned long long)));
-    A.stamps = stamp_buf;
-#endif
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    A.nvirt = std::min(std::min(A.p.tiles_x * A.p.tiles_y, cus), MFMA_PARTIALS);
-    // a background pass (beside a training stream that holds the other half of the CUs) launches half as many
-    // workgroups, each walking two virtual ones
-    const int grid = background ? std::max(1, A.nvirt / 2) : A.nvirt;   // (a quarter / a sixth: 3 / 10 ms per tile slower)
-    int rc;
-    if (mode == MODE_DECODE) {
-        rc = A.p.NT == 1 ? launch_apply<1, MODE_DECODE>(A, grid, s)
-           : A.p.NT == 2 ? launch_apply<2, MODE_DECODE>(A, grid, s)
-                         : launch_apply<4, MODE_DECODE>(A, grid, s);
-    } else {
-        rc = mode == MODE_EVAL_X16
-                 ? (A.p.NT == 1 ? launch_apply<1, MODE_EVAL_X16>(A, grid, s, background) : launch_apply<2, MODE_EVAL_X16>(A, grid, s, background))
-             : mode == MODE_EVAL_FAST
-                 ? (A.p.NT == 1 ? launch_apply<1, MODE_EVAL_FAST>(A, grid, s, background)
-                    : A.p.NT == 2 ? launch_apply<2, MODE_EVAL_FAST>(A, grid, s, background)
-                                  // bc = 128: the tolerance arithmetic's extra operands spill at two waves per SIMD (88 registers,
-                                  // 356 B of scratch when it was instantiated); the canonical pass IS within the 1e-6 the flag promises
-                                  : launch_apply<4, MODE_EVAL>(A, grid, s, background))
-                 : (A.p.NT == 1 ? launch_apply<1, MODE_EVAL>(A, grid, s, background)
-                    : A.p.NT == 2 ? launch_apply<2, MODE_EVAL>(A, grid, s, background)
-                                  : launch_apply<4, MODE_EVAL>(A, grid, s, background));
-        if (rc) return rc;
-        k_sum_partials_mfma<<<1, 64, 0, s>>>(partial, A.nvirt, sse);
-        LBDRN_LAUNCH_CHECK();
-    }
-#ifdef LBDRN_APPLY_STAMPS
-    if (rc == 0) {
-        LBDRN_HIP_TRY(hipStreamSynchronize(s));
-        unsigned long long h[1024 * 8];
-        LBDRN_HIP_TRY(hipMemcpy(h, A.stamps, (size_t)grid * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        double sum[8] = {};
-        for (int b = 0; b < grid; ++b) for (int k = 0; k < 8; ++k) sum[k] += (double)h[b * 8 + k];
-        const double blocks = (double)A.p.tiles_x * A.p.tiles_y * A.p.TH * (TILE_W / 32) / APPLY_WAVES / grid;
-        fprintf(stderr, "[lbdrn apply stamps] per wave: tiles-staging %.0f total; per 32-px block: L0 %.0f sin %.0f hidden %.0f last %.0f epilogue %.0f\n",
-                sum[0] / grid, sum[1] / grid / blocks, sum[2] / grid / blocks, sum[3] / grid / blocks, sum[4] / grid / blocks, sum[5] / grid / blocks);
-    }
-#endif
-    return rc;
+    return run_pass(A, c, mode, packed, partial, dispatch_apply);
 }
 
 int mfma_decode(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* msb, const float* params,
                 uint16_t* out, float* y_out, void* ws, size_t ws_bytes, hipStream_t s)
 {
-    return run_apply(g, net, MODE_DECODE, nullptr, msb, params, out, y_out, nullptr, ws, ws_bytes, false, s);
+    return run_apply({g, net, nullptr, msb, params, out, y_out, nullptr, ws, ws_bytes, false, s}, MODE_DECODE);
 }
 
 int mfma_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                   const uint16_t* msb, const float* params, double* sse, void* ws, size_t ws_bytes,
                   bool background, bool fast, bool x16, hipStream_t s)
 {
-    return run_apply(g, net, fast ? (x16 ? MODE_EVAL_X16 : MODE_EVAL_FAST) : MODE_EVAL, img, msb, params, nullptr, nullptr, sse, ws, ws_bytes,
-                     background, s);
+    return run_apply({g, net, img, msb, params, nullptr, nullptr, sse, ws, ws_bytes, background, s},
+                     fast ? (x16 ? MODE_EVAL_X16 : MODE_EVAL_FAST) : MODE_EVAL);
 }
 
 }  // namespace lbdrn

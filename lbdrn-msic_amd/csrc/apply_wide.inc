@@ -45,7 +45,7 @@ __host__ __device__ __forceinline__ int wa_feat_of_slot(int j, int P2, int S2, b
 
 static bool make_wapply_plan(const lbdrn_geom& g, const lbdrn_net& net, WApplyPlan* p, bool fast = false)
 {
-    if (net.act != LBDRN_ACT_SINE || (net.bc != 128 && net.bc != 256)) return false;
+    if (net.act != LBDRN_ACT_SINE || net.bc % 16 != 0 || !wapply_row(net.bc / 16)) return false;
     if (net.C > 16 || net.nl < 1 || net.nl > 2 || net.F < 1) return false;
     WApplyPlan q;
     q.NT = net.bc / 16;

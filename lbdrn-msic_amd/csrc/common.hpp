@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "../../include/lbdrn_hip.h"
 
 namespace lbdrn {
@@ -50,6 +52,21 @@ inline int feature_dim(const lbdrn_geom& g)
     return 2 * g.P + (g.use_colors ? g.C * side * side : 0);
 }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// the dynamic-LDS ceiling of a kernel is told to the runtime once per device and kernel (a cache of an idempotent
+// setting; several host threads may get here together)
+template <class K>
+static int configure_lds_once(K kern, int bytes, std::atomic<unsigned long long>& configured)
+{
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(configured.load(std::memory_order_relaxed) & bit)) {
+        LBDRN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        configured.fetch_or(bit, std::memory_order_relaxed);
+    }
+    return 0;
+}
 
 int check_geom(const lbdrn_geom* g);
 int check_net(const lbdrn_net* n);

@@ -34,7 +34,6 @@
 //
 // Training parity is a tolerance contract (1e-5 relative on the loss), not a bit
 // pattern: the summation order differs from the generic kernels and from torch.
-#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <utility>
@@ -1171,21 +1170,6 @@ __device__ __forceinline__ float wave_sum(float x)
     const float a = __int_as_float(__builtin_amdgcn_readlane(xi, 15)), b = __int_as_float(__builtin_amdgcn_readlane(xi, 31));
     const float c = __int_as_float(__builtin_amdgcn_readlane(xi, 47)), d = __int_as_float(__builtin_amdgcn_readlane(xi, 63));
     return (a + b) + (c + d);
-}
-
-// the dynamic-LDS ceiling of a kernel is told to the runtime once per device and kernel (a cache of an idempotent
-// setting; several host threads may get here together)
-template <class K>
-static int configure_lds_once(K kern, int bytes, std::atomic<unsigned long long>& configured)
-{
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(configured.load(std::memory_order_relaxed) & bit)) {
-        LBDRN_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        configured.fetch_or(bit, std::memory_order_relaxed);
-    }
-    return 0;
 }
 
 // measurement aid (see lbdrn_hip.h): mode 1 doubles the reduce/Adam launch of every step, mode 2 the training launch,

@@ -1,6 +1,7 @@
 """Randomised shapes: the fused MFMA kernels against the generic kernels (bit-exact for apply, training
 tolerance for the step) and, on a subsample, against the oracle.  Seeds are fixed: the cases are the same
 every run."""
+import ctypes
 import os
 
 import numpy as np
@@ -83,6 +84,54 @@ def test_apply_fuzz_mfma_equals_generic_and_oracle(dev):
             assert np.array_equal(ops.from_device_u16(a), ro), tag
             checked_oracle += 1
     assert ran >= 10 and checked_oracle >= 3 and relus >= 2, (ran, checked_oracle, relus)
+
+
+@pytest.mark.parametrize("act", ["sine", "relu"])
+@pytest.mark.parametrize("nl", [1, 2])
+def test_apply_at_bc96_runs_the_generic_kernels_and_the_fused_pass_refuses_it(dev, nl, act):
+    """bc = 96 (the width no case above draws) would be NT = 3 hidden tiles, and no fused apply kernel is built for three
+    (APPLY_INSTANCES, csrc/apply_mfma.hip): LBDRN_PATH_AUTO decodes and evaluates on the generic kernels -- the raster and y
+    bit for bit PATH_GENERIC's and the oracle's, the sum within the 1e-11 this file holds the paths to --, and LBDRN_PATH_MFMA
+    answers LBDRN_E_UNSUPPORTED from both entry points without writing its output.  70 columns: a full and a ragged 64-column
+    tile; 20 rows: a ragged tile row."""
+    C, H, W, K, D, bc = 3, 20, 70, 5, 1, 96
+    rng = np.random.default_rng(9600 + 10 * nl + (act == "relu"))
+    cfg = FeatCfg(False, False, 1.4, 12, True, True, act)
+    F = cfg.feature_dim(C, D)
+    img = rng.integers(0, 10001, (C, H, W)).astype(np.uint16)
+    msb = img >> K
+    mx = int(msb.max())
+    assert mx > 0
+    geom = ops.FeatureGeometry(C, H, W, K, D, mx, cfg, dev)
+    net = ops.make_net(F, bc, C, nl, cfg.act)
+    pn = _params(rng, F, bc, C, nl, 2.5 * (30.0 if cfg.act else 1.0))
+    p = torch.from_numpy(pn).to(dev)
+    msb_d, img_d = ops.to_device_u16(msb, dev), ops.to_device_u16(img, dev)
+    a, ya = ops.decode_fused(geom, net, msb_d, p, want_y=True, path=ops.PATH_AUTO)
+    b, yb = ops.decode_fused(geom, net, msb_d, p, want_y=True, path=GEN)
+    assert torch.equal(a, b) and torch.equal(ya.view(torch.int32), yb.view(torch.int32))
+    with O.hidden_activation(cfg.activation):
+        ro = O.decode(msb, K, D, O.FeatCfg(False, False, 1.4, 12, True, True), pn, bc, nl, mx)
+    assert np.array_equal(ops.from_device_u16(a), ro)
+    assert np.unique(ro & ((1 << K) - 1)).size > 2          # (the outputs move: not a flat 0.5)
+    s1 = float(ops.eval_sse(geom, net, img_d, msb_d, p, path=ops.PATH_AUTO).item())
+    s2 = float(ops.eval_sse(geom, net, img_d, msb_d, p, path=GEN).item())
+    assert s2 > 0 and abs(s1 - s2) <= 1e-11 * max(s2, 1e-30), (s1, s2)
+    # the fused pass: refused, and the buffers it would have written are as they were
+    ws = ops.ApplyWorkspace(geom, net, dev)
+    out = torch.full_like(msb_d, 0x5A5A)
+    y = torch.full((H * W, C), -7.25, dtype=torch.float32, device=dev)
+    sse = torch.full((1,), -3.5, dtype=torch.float64, device=dev)
+    ptr = ops._ptr
+    with pytest.raises(ops._lib.LbdrnError) as e:
+        ops._call(ops._lib.lib().lbdrn_decode_fused, msb_d, ctypes.byref(geom.c), ctypes.byref(net), ptr(msb_d), ptr(p), ptr(out), ptr(y),
+                  ptr(ws.buf), ws.nbytes, MFMA)
+    assert e.value.code == ops._lib.E_UNSUPPORTED
+    with pytest.raises(ops._lib.LbdrnError) as e:
+        ops.eval_sse(geom, net, img_d, msb_d, p, path=MFMA, ws=ws, out=sse)
+    assert e.value.code == ops._lib.E_UNSUPPORTED
+    torch.cuda.synchronize(dev)
+    assert bool((out == 0x5A5A).all()) and bool((y == -7.25).all()) and float(sse.item()) == -3.5
 
 
 def test_apply_fuzz_streaming_kernel_equals_generic_and_oracle(dev):

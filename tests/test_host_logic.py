@@ -52,6 +52,47 @@ def test_geometry_helpers_without_device():
     assert rel(64, 2, 250) == (242, L.lbdrn_train_group_max())   # configs[4]: 50 positional + 192 colour features
 
 
+def test_apply_workspace_at_bc96_is_the_generic_sizing_and_unchanged_elsewhere():
+    """bc = 96 would be NT = 3 hidden tiles, and no k_apply_mfma<3, ..> is built (APPLY_INSTANCES, csrc/apply_mfma.hip): the fused
+    apply pass does not plan it, so lbdrn_apply_workspace is generic_apply_workspace alone -- the feature chunk, the output chunk,
+    lbdrn_forward_workspace of the chunk and the 256 SSE partials (csrc/generic.hip).  At bc = 32 / 64 / 128 / 256 the size is what
+    it was before the instance lists: the constants are the answers of the library built from the commit before them, for
+    (C, H, W, D, relative, P, F, nl, act) with K = 5, colours on; on the small rasters the fused sizing is the larger one."""
+    from lbdrn_hip import _lib
+    L = _lib.lib()
+    before = {
+        (8, 2048, 2048, 2, 1, 0, 200, 2, 0): {32: 71305216, 64: 88082432, 128: 121636864, 256: 188745728},   # the headline shape
+        (8, 5, 7, 2, 1, 0, 200, 2, 0): {32: 54016, 64: 107520, 128: 197888, 256: 518400},
+        (8, 5, 7, 2, 1, 25, 250, 1, 0): {32: 47616, 64: 81152, 128: 148224, 256: 288000},
+        (3, 4, 4, 1, 1, 0, 27, 1, 1): {32: 17152, 64: 25344, 128: 41984, 256: 36864},
+        (4, 4, 6, 3, 0, 0, 196, 2, 0): {32: 42752, 64: 84992, 128: 197888, 256: 518400},
+        (16, 3, 3, 1, 1, 1, 146, 2, 1): {32: 35840, 64: 71168, 128: 17408, 256: 26624},
+    }
+    tables = (ctypes.c_float * (2048 * 25))()
+    up = lambda n: (n + 255) // 256 * 256
+
+    def sizes(shape, bc):
+        C, H, W, D, rel, P, F, nl, act = shape
+        tab = ctypes.addressof(tables) if P else None      # (sizing reads no table; it wants them present)
+        g = _lib.Geom(C, H, W, 5, D, 100, 1, rel, P, 0, tab, tab)
+        assert L.lbdrn_feature_dim(ctypes.byref(g)) == F
+        net = _lib.Net(F, bc, C, nl, act)
+        chunk = min(65536, H * W)
+        generic = up(chunk * F * 4) + up(chunk * C * 4) + L.lbdrn_forward_workspace(ctypes.byref(net), chunk) + up(256 * 8)
+        return L.lbdrn_apply_workspace(ctypes.byref(g), ctypes.byref(net)), generic
+
+    fused_larger = 0
+    for shape, was in before.items():
+        for bc, n in was.items():
+            got, generic = sizes(shape, bc)
+            assert got == n and got >= generic, (shape, bc, got, n, generic)
+            fused_larger += got > generic
+        got, generic = sizes(shape, 96)
+        assert got == generic > 0, (shape, got, generic)
+    assert sizes((8, 2048, 2048, 2, 1, 0, 200, 2, 0), 64)[1] == 88082432    # (the restated generic sizing is the library's)
+    assert fused_larger >= 12
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU behaviour")
 def test_compute_fails_loudly_without_gpu():
     from lbdrn_hip import _lib, ops

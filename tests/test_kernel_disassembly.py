@@ -156,3 +156,33 @@ def test_the_training_kernels_in_the_library_are_exactly_the_listed_instances(tm
                 found.add(("tile", a[0], a[1], 0, "sine"))
     built = set(R.built_instances())
     assert found == built, (sorted(found - built), sorted(built - found))
+
+
+def test_the_apply_kernels_in_the_library_are_exactly_the_listed_instances(tmp_path):
+    """Kernel symbols only, the twin of the test above for the fused apply pass: the k_apply_mfma<NT, MODE, RELU> and
+    k_apply_wide<NT, NL, MODE> instances in the shipped library's gfx950 code object are the ones APPLY_INSTANCES (each row for
+    Sine and ReLU) and WAPPLY_INSTANCES (each row in the decode, the canonical and the fast evaluation mode) of
+    csrc/apply_mfma.hip name: 20 and 12."""
+    so = os.path.join(ROOT, "lbdrn-msic_amd", "liblbdrn_hip.so")
+    if not (os.path.exists(OBJDUMP) and os.path.exists(so)):
+        pytest.skip("llvm-objdump or the library is missing")
+    src = open(os.path.join(ROOT, "lbdrn-msic_amd", "csrc", "apply_mfma.hip")).read()
+    modes = {name: int(v) for name, v in re.findall(r"\b(MODE_[A-Z0-9_]+) = (\d+)", src)}
+    assert modes == {"MODE_DECODE": 0, "MODE_EVAL": 1, "MODE_EVAL_FAST": 2, "MODE_EVAL_X16": 3}
+    rows = [(int(nt), modes[m]) for nt, m in re.findall(r"\bX\((\d+), (MODE_[A-Z0-9_]+)\)", src)]
+    wrows = [(int(nt), int(nl)) for nt, nl in re.findall(r"\bX\((\d+), (\d+)\)", src)]
+    listed = {("mfma", nt, m, relu) for nt, m in rows for relu in ("false", "true")} | \
+             {("wide", nt, nl, m) for nt, nl in wrows for m in (modes["MODE_DECODE"], modes["MODE_EVAL"], modes["MODE_EVAL_FAST"])}
+    assert len(rows) == len(set(rows)) == 10 and len(wrows) == len(set(wrows)) == 4 and len(listed) == 32
+    work = tmp_path / "co"
+    work.mkdir()
+    shutil.copy(so, work / "lib.so")
+    subprocess.run([OBJDUMP, "--offloading", "lib.so"], cwd=work, check=True, capture_output=True)   # unbundles next to the input
+    found = set()
+    for co in sorted(work.glob("lib.so.*gfx950")):
+        syms = subprocess.run([OBJDUMP, "--syms", "-C", str(co)], capture_output=True, text=True, check=True).stdout
+        for nt, m, relu in re.findall(r"\blbdrn::k_apply_mfma<(\d+), (\d+), (true|false)>\(", syms):
+            found.add(("mfma", int(nt), int(m), relu))
+        for nt, nl, m in re.findall(r"\blbdrn::k_apply_wide<(\d+), (\d+), (\d+)>\(", syms):
+            found.add(("wide", int(nt), int(nl), int(m)))
+    assert found == listed, (sorted(found - listed), sorted(listed - found))
