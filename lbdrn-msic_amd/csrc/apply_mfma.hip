@@ -26,6 +26,7 @@
 namespace lbdrn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
@@ -395,6 +396,55 @@ __device__ __forceinline__ float apply_hidden_act(float z)
     else return mode_fast(MODE) ? fast_sin(30.0f * z) : siren_act(z);
 }
 
+// The last layer (bc -> C, C <= 8) of the tolerance-arithmetic pass on v_mfma_f32_4x4x1_16B_f32: sixteen independent 4x4 outer
+// products per instruction, block b = lane / 4, D_b[i][j] += A_b[i] B_b[j] with A_b[i] in lane 4 b + i, B_b[j] in lane 4 b + j and
+// D_b[i][j] in register i of lane 4 b + j (scripts/mfma4_probe.hip checks the map and times the instruction).  The hidden
+// activations already sit where B wants them -- lane 32 h + j holds pixel j, register r unit 2 r + h --, so with
+// A = W_last[4 g + (lane & 3)][unit] every lane collects four channels of ITS pixel over the units of ITS half's parity:
+// NG = (C + 3) / 4 instructions per hidden register where the 32x32x2 tile spends 64 cycles of the matrix pipe on 32 rows, 24 of
+// them padding at C = 8.  The A operand comes out of the fragments as they are packed for the 32x32x2 step: row 4 g + (lane & 3)
+// of lane half h is entry 32 h + 4 g + (lane & 3) of step s (four addresses per half, broadcast: no bank conflict).  The halves
+// are joined by one v_permlane32_swap and one add per register, after which half h holds channels 4 h .. 4 h + 3 complete -- the
+// channels the epilogue finishes in that half, out of registers 0..3 of o as before.  The sum's order: bias + even units
+// ascending, the odd units ascending from zero, then the two (held to 1e-6 of the canonical sum, not to its bits).
+// wl: the [bc/2][64] fragments; bl: the last bias as packed, [h][16] with entry r < 4 of half g = bias[4 g + r].
+template <int NT, int NG>
+__device__ __forceinline__ void last_layer_4x4(f32x16& o, const f32x16 (&hid)[NT], const float* wl, const float* bl, int lane)
+{
+    const bool lo = lane < 32;
+    f32x4 part[NG];
+#pragma unroll
+    for (int gq = 0; gq < NG; ++gq) {
+        const float4 b4 = *reinterpret_cast<const float4*>(bl + gq * 16);
+        part[gq][0] = lo ? b4.x : 0.0f; part[gq][1] = lo ? b4.y : 0.0f;
+        part[gq][2] = lo ? b4.z : 0.0f; part[gq][3] = lo ? b4.w : 0.0f;
+    }
+    // every fragment is read before the first product: an instruction this short (4.5 cycles of the pipe, 16 until its result
+    // can be accumulated on) hides no LDS latency behind itself the way a 64-cycle 32x32x2 does
+    const float* wq = wl + (lane & 32) + (lane & 3);
+    float a[NT * 16][NG];
+#pragma unroll
+    for (int s = 0; s < NT * 16; ++s)
+#pragma unroll
+        for (int gq = 0; gq < NG; ++gq) a[s][gq] = wq[s * 64 + 4 * gq];
+    __builtin_amdgcn_sched_barrier(0);   // (or the scheduler sinks each read to just before its product again)
+#pragma unroll
+    for (int s = 0; s < NT * 16; ++s) {
+        const float b = hid[s / 16][s % 16];
+#pragma unroll
+        for (int gq = 0; gq < NG; ++gq) part[gq] = __builtin_amdgcn_mfma_f32_4x4x1f32(a[s][gq], b, part[gq], 0, 0, 0);
+    }
+    // swap(x, y): lanes 32..63 of x <-> lanes 0..31 of y.  x = group 0, y = group NG - 1: afterwards x is [group 0 | group NG-1]
+    // of the even units, y the same of the odd units
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float x = part[0][i], y = part[NG - 1][i];   // (scalars first: a bit cast of a vector ELEMENT reads element 0)
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(y), false, false);
+        const unsigned even = sw[0], odd = sw[1];
+        o[i] = __uint_as_float(even) + __uint_as_float(odd);
+    }
+}
+
 template <int NT, int MODE, bool RELU>
 __global__ void __launch_bounds__(APPLY_THREADS) k_apply_mfma(ApplyArgs A)
 {
@@ -669,19 +719,24 @@ __global__ void __launch_bounds__(APPLY_THREADS) k_apply_mfma(ApplyArgs A)
             ASTAMP(3);  // hidden layers incl. their sin
             // ---- last layer: rows = channels
             f32x16 o;
+            if (mode_fast(MODE)) {   // (C <= 8: run_apply) 4x4 blocks, no padded rows (registers 0..3 of o: channels 4 h .. 4 h + 3, as below)
+                if (C > 4) last_layer_4x4<NT, 2>(o, hid, wl, bl, lane);
+                else last_layer_4x4<NT, 1>(o, hid, wl, bl, lane);
+            } else {
 #pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                float4 b4 = *reinterpret_cast<const float4*>(bl + h * 16 + q4 * 4);
-                o[q4 * 4 + 0] = b4.x; o[q4 * 4 + 1] = b4.y; o[q4 * 4 + 2] = b4.z; o[q4 * 4 + 3] = b4.w;
-            }
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    float4 b4 = *reinterpret_cast<const float4*>(bl + h * 16 + q4 * 4);
+                    o[q4 * 4 + 0] = b4.x; o[q4 * 4 + 1] = b4.y; o[q4 * 4 + 2] = b4.z; o[q4 * 4 + 3] = b4.w;
+                }
 #pragma unroll
-            for (int s = 0; s < NT * 16; ++s) {
-                float b = hid[s / 16][s % 16];
-                float a = wl[s * 64 + lane];
-                o = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, o, 0, 0, 0);
+                for (int s = 0; s < NT * 16; ++s) {
+                    float b = hid[s / 16][s % 16];
+                    float a = wl[s * 64 + lane];
+                    o = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, o, 0, 0, 0);
+                }
             }
             ASTAMP(4);  // last layer
-            // ---- epilogue
+            // ---- epilogue (the 4x4-block last layer writes o[0..3] only: it runs with C <= 8, where nreg is 4 and no other entry is read)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ch = acc_row(r, h);
@@ -787,6 +842,10 @@ static int launch_pass(const Args& A, int grid, hipStream_t s, bool whole_lds)
 static int dispatch_apply(const ApplyArgs& A, int mode, int grid, hipStream_t s, bool whole_lds)
 {
     const bool relu = A.net.act == LBDRN_ACT_RELU;
+    if (mode_fast(mode) && A.net.C > 8) {   // (last_layer_4x4 finishes channels 0..7)
+        set_error("the fast instances of the fused apply pass take at most 8 bands, not %d", A.net.C);
+        return LBDRN_E_UNSUPPORTED;
+    }
 #define X(nt, m)                                                                                                       \
     if (A.p.NT == nt && mode == m)                                                                                     \
         return relu ? launch_pass<k_apply_mfma<nt, m, true>, APPLY_THREADS, true>(A, grid, s, whole_lds)               \
@@ -908,8 +967,14 @@ static int run_apply(const ApplyCall& c, int mode)
         ApplyPlan fp, xp;
         if (make_plan(g, net, &fp, true, false) && (!make_plan(g, net, &xp, true, true) || xp.TH < fp.TH)) mode = MODE_EVAL_FAST;
     }
+    // The fast instances of k_apply_mfma carry the 4x4-block last layer only (C <= 8; with the 32x32x2 one beside it <2, 2, *> needs
+    // 256 registers and spills three): with more bands than that NO fast plan is made for this kernel -- the pass is the canonical
+    // one, which IS within the 1e-6 the flag promises (DESIGN.md 4.6 prices it), and where the canonical plan does not fit, the
+    // streaming kernel's or none.  dispatch_apply refuses a fast launch with C > 8 should one ever be asked for.
+    const int requested = mode;
+    if (mode_fast(mode) && net.C > 8) mode = MODE_EVAL;
     if (!make_plan(g, net, &A.p, mode_fast(mode), mode == MODE_EVAL_X16))   // too wide for LDS-resident weights: the streaming kernel (apply_wide.inc)
-        return run_wapply(c, mode);
+        return run_wapply(c, requested);
     mode = serving_mode(mode, A.p.NT, A.p.x16);   // (x16 is a hint: where the shape or the image does not qualify, the pass is the fast one)
     if (int rc = workspace_holds(c, mfma_apply_workspace(g, net))) return rc;
     float* packed = (float*)c.ws;
