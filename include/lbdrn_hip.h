@@ -208,9 +208,14 @@ int lbdrn_train_epoch(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t 
                       int32_t path, void *stream);
 
 /* The same epoch for `count` (1 .. lbdrn_train_group_max()) INDEPENDENT fits of one shape -- same raster dimensions,
- * K, D, feature switches, network, n, batch size, Adam step count and learning rate; every array holds one entry per
- * fit: its geometry (msb_max and tables may differ), image, MSB plane, permutation, optimiser state, losses (array or
- * entries may be NULL) and its own prepared workspace of workspace_bytes each.  Where the shape has a fused step that
+ * D, feature switches, network, n, batch size, Adam step count and learning rate; every array holds one entry per
+ * fit: its geometry (K, msb_max and tables may differ), image, MSB plane, permutation, optimiser state, losses (array or
+ * entries may be NULL) and its own prepared workspace of workspace_bytes each.  K may differ because, like msb_max, it is
+ * read by the row build of lbdrn_train_prepare only: the rows and labels of a fit lie in its workspace before the first
+ * step, and no stepping kernel, reduce launch or launch plan looks at K (the fits of one image's K sweep are such a
+ * group).  perm[f] entries may alias -- one permutation for several fits: every launch only reads through perm (the
+ * kernels take it as const int64_t *, none stores to it), so the fits of a group cannot disturb one another there.
+ * Everything else a fit writes -- params, exp_avg, exp_avg_sq, losses, workspace -- must be its own.  Where the shape has a fused step that
  * takes groups, minibatch s of every fit runs in ONE launch (two 8192-row minibatches = 256 workgroups fill the
  * chip exactly; independent chains of 128-workgroup launches meet each other only by chance), otherwise the fits
  * run one after another.  The reference has no such call (run.sh:29-42 encodes image after image): results are those

@@ -332,7 +332,9 @@ int lbdrn_train_epoch_group(int32_t count, const lbdrn_geom* const* g, const lbd
         LBDRN_REQUIRE(g[f] && img[f] && msb[f] && perm[f] && params[f] && exp_avg[f] && exp_avg_sq[f], "null pointer (fit %d)", f);
         if (int rc = check_geom(g[f])) return rc;
         if (int rc = net_matches(g[f], net)) return rc;
-        LBDRN_REQUIRE(g[f]->C == g[0]->C && g[f]->H == g[0]->H && g[f]->W == g[0]->W && g[f]->K == g[0]->K &&
+        // (K, like msb_max, may differ: only the row build of lbdrn_train_prepare reads it, and the sequential calls below
+        // take g[f])
+        LBDRN_REQUIRE(g[f]->C == g[0]->C && g[f]->H == g[0]->H && g[f]->W == g[0]->W &&
                       g[f]->D == g[0]->D && g[f]->P == g[0]->P && g[f]->use_colors == g[0]->use_colors &&
                       g[f]->relative == g[0]->relative, "the fits of a group must have one shape (fit %d differs)", f);
     }

@@ -146,6 +146,15 @@ def train_tiles(args, tiles, draws):
     return results
 
 
+def train_tiles_at(args, arrays, Ks, draws):
+    """train_tiles for fits that each bring their K (main_k_points: the tiles of one image at several K; an array or a
+    FitDraws that serves several entries is the same object in every one of them) -> one result per entry, or the
+    exception that fit ended with."""
+    return codec.fit_images(arrays, Ks, args.D, args.base_channel, args.num_layers, args.lr, args.batch_size, args.epochs,
+                            args.val_duration, cfg=FeatCfg.from_constants(), device=DEVICE, host_msb=False, draws=draws,
+                            in_flight=IN_FLIGHT, errors="return")
+
+
 def _host_msb(res):
     from lbdrn_hip import ops
     msb = ops.from_device_u16(res.msb_device)
@@ -286,6 +295,127 @@ def main(argv=None, shard_tiles=None):
     if world > 1:
         shard.finish()
     return 0
+
+
+def output_folder(args):
+    """The directory main() writes a point into (ref encode.py:207-209)."""
+    filename = os.path.splitext(os.path.basename(args.path))[0]
+    return "{}/{}_r{}_K{}_bc{}_nl{}_D{}_prec{}_lr{}_bs{}_e{}".format(
+        args.output_dir, filename, args.split_ratio, args.K, args.base_channel, args.num_layers,
+        args.D, args.precision, args.lr, args.batch_size, args.epochs)
+
+
+def main_k_points(argv, Ks):
+    """main() for several K of ONE raster, their fits side by side on the device: what `main(argv + ["-K", k])` for k in
+    Ks writes, one after another -- the same directories, .bin bytes and encode.txt records (only the records' times
+    differ: the `Time elapsed` record, the seconds of the `fit ...s on` record and of the jp2 `waited ...s more` one).
+    Every point of a sweep re-seeds its generator (ref encode.py:200-205), so the K points of a raster have the same
+    tiles, the same initial weights and the same minibatch orders: the raster is read and tiled once, the draws are made
+    once per tile, and all (tile, K) fits go through one codec.fit_many, tile-major, so that the K points of a tile --
+    one shape -- step in one launch per minibatch (codec.fit_group).  Then every K is reported and packed as main() does
+    it.  One process, one GPU: the tiles are not spread over ranks (sweep.py deals whole points).  A -K in argv is
+    ignored.  Returns {K: None, or the exception that point ended with}; a point that fails does not stop the others."""
+    parser = build_parser()
+    base = parser.parse_args(argv)
+    Ks = [int(k) for k in Ks]
+    if os.environ.get("LBDRN_WEIGHTS_CODEC") != "fpzip":
+        try:
+            container.check_weight_precision(base.precision)
+        except ValueError as e:
+            parser.error(str(e))
+    if base.max_error is not None and not 0 <= base.max_error <= 65535:
+        parser.error(f"--max-error {base.max_error}: 0 (lossless) .. 65535")
+    try:
+        container.check_base_codec(BASE_CODEC)
+    except ValueError as e:
+        parser.error(str(e))
+    if not base.randomness:
+        torch.manual_seed(base.seed)
+        np.random.seed(base.seed)
+        random.seed(base.seed)
+    org_path = base.path
+    filename = os.path.splitext(os.path.basename(org_path))[0]
+    outcome, point, todo = {}, {}, []
+    for K in Ks:
+        a = argparse.Namespace(**vars(base))
+        a.K = K
+        a.output_dir = output_folder(a)
+        os.makedirs(a.output_dir, exist_ok=True)
+        point[K] = a
+        bitstream_path, log_path = f"{a.output_dir}/{filename}.bin", f"{a.output_dir}/encode.txt"
+        done = False
+        if os.path.exists(log_path) and os.path.exists(bitstream_path):
+            with open(log_path) as f:
+                done = "Time elapsed" in f.read()
+        if done:
+            print("Bitstream already created!")
+            outcome[K] = None
+        else:
+            todo.append(K)
+    if not todo:
+        return outcome
+    start_time = time.time()
+    try:
+        img = raster_io.read_raster(org_path)
+        img = img.reshape((-1,) + img.shape[-2:])
+        height, width = img.shape[-2:]
+        windows = list(tile_windows(width, height, base.split_ratio)) if base.split_ratio > 1 else [None]
+        C = img.shape[0]
+        n_feature = FeatCfg.from_constants().feature_dim(C, base.D)
+        # one draw per tile, in tile order, serves every K (read-only: codec.fit_group)
+        draws = [codec.draw_fit(n_feature, base.base_channel, C, base.num_layers, base.epochs, base.val_duration)
+                 for _ in windows]
+        tiles = []
+        for win in windows:
+            tile = img
+            if win is not None:
+                i, j, x0, y0, w, h = win
+                tile = np.ascontiguousarray(img[:, y0:y0 + h, x0:x0 + w])
+            tiles.append(tile)
+        ahead = {}
+        if BASE_CODEC.lower() in ("jp2", "jpeg2000", "jp2openjpeg") and os.environ.get("LBDRN_JP2_AHEAD", "1") != "0":
+            ahead = {K: BasePayloadsAhead(tiles, K) for K in todo}
+        entries = [(t, K) for t in range(len(tiles)) for K in todo]      # tile-major: the K points of a tile are neighbours
+        results = train_tiles_at(base, [tiles[t] for t, _ in entries], [K for _, K in entries], [draws[t] for t, _ in entries])
+        results = dict(zip(entries, results))
+    except Exception as e:      # nothing of this raster can be written: every open point ends with it
+        for K in todo:
+            outcome[K] = e
+        return outcome
+    shared_seconds = (time.time() - start_time) / len(todo)
+    for K in todo:
+        a = point[K]
+        t_point = time.time()
+        try:
+            for t in range(len(tiles)):
+                if isinstance(results[(t, K)], Exception):
+                    raise results[(t, K)]
+            logger.create_logger(a.output_dir, "encode.txt")
+            tiles_out = []
+            for t, (win, tile) in enumerate(zip(windows, tiles)):
+                a.path = org_path if win is None else f"{a.output_dir}/tile_{win[0]}_{win[1]}.tif"
+                res = results[(t, K)]
+                take = (lambda t=t, K=K: ahead[K].take(t)) if K in ahead else None
+                logger.log.info(a)
+                nn, base_payload = report_and_pack(a, res, take)
+                layer = residual_layer(a, res, tile, nn) if a.max_error is not None else None
+                tiles_out.append((nn, base_payload, layer))
+            header = container.pack_header(a.split_ratio, width, height, K, a.base_channel, a.num_layers, a.D,
+                                           [len(rec[0]) for rec in tiles_out], [len(rec[1]) for rec in tiles_out],
+                                           activation=FeatCfg.from_constants().activation)
+            with open(f"{a.output_dir}/{filename}.bin", "wb") as f:
+                f.write(header)
+                for nn, base_payload, _ in tiles_out:
+                    f.write(nn)
+                    f.write(base_payload)
+                if a.max_error is not None:
+                    f.write(container.pack_residual_trailer(a.max_error, [rec[2] for rec in tiles_out]))
+            # this point's share of the reading and fitting all points did together, plus its own reporting and packing
+            logger.log.info(f"Time elapsed: {shared_seconds + time.time() - t_point}")
+            outcome[K] = None
+        except Exception as e:
+            outcome[K] = e
+    return outcome
 
 
 if __name__ == "__main__":

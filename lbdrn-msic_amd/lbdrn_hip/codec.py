@@ -148,14 +148,32 @@ def device_shared():
     return os.environ.get("LBDRN_DEVICE_SHARED", "0") not in ("", "0")
 
 
+def k_per_fit(K, count):
+    """`K` of fit_group / fit_many as one K per fit: an int is every fit's K (the tiles of one image, independent images
+    of one encode setting), a sequence brings one per image (the K points of a sweep: the same raster several times)."""
+    if isinstance(K, (int, np.integer)):
+        return [int(K)] * count
+    Ks = [int(k) for k in K]
+    if len(Ks) != count:
+        raise ValueError(f"{len(Ks)} values of K for {count} images: one K, or one per image")
+    return Ks
+
+
+def image_bytes(C, H, W):
+    """The raster itself in HBM (uint16 planes): the part of fit_bytes that fits of ONE device tensor share."""
+    return C * H * W * 2
+
+
 def fit_bytes(C, H, W, K, D, base_channel, num_layers, batch_size, epochs, cfg=None):
     """Device bytes one fit of this shape holds while it runs (fit_device): the training workspace -- dominated by the
     [N][F + C] row matrix, 832 B a pixel at the headline shape --, the permutations of all epochs and their scratch, the
     image, its MSB plane and the decoded raster, the evaluation workspace, snapshots.  What fit_many divides the free
-    memory by."""
+    memory by.  K: an int, or several (the largest of their fits)."""
+    if not isinstance(K, (int, np.integer)):
+        return max(fit_bytes(C, H, W, int(k), D, base_channel, num_layers, batch_size, epochs, cfg) for k in K)
     cfg = cfg or FeatCfg.from_constants()
     N = H * W
-    g = ops._lib.Geom(C, H, W, K, D, 1, int(cfg.use_colors), int(cfg.relative), int(cfg.P), 0, None, None)
+    g = ops._lib.Geom(C, H, W, int(K), D, 1, int(cfg.use_colors), int(cfg.relative), int(cfg.P), 0, None, None)
     net = ops.make_net(cfg.feature_dim(C, D), base_channel, C, num_layers, cfg.act)
     L = ops.lib()
     import ctypes
@@ -178,7 +196,8 @@ def default_in_flight(C, H, W, K, D, base_channel, num_layers, cfg=None, path=No
     * the generic path is many small launches per step: 4.
     The wide bc = 64 step (D = 3 on 6..8 bands) is one k_train_split launch of 256 workgroups of 156 KB per fit
     and minibatch, groups included: the reduce / Adam launch (4 KB) still fits beside it, and 4 in flight as pairs measured
-    123 ms per tile against 157 alone (profiles/wide_window_timing.txt)."""
+    123 ms per tile against 157 alone (profiles/wide_window_timing.txt).
+    K (an int or one per fit) does not enter: no stepping kernel reads it."""
     cfg = cfg or FeatCfg.from_constants()
     if path == ops._lib.PATH_GENERIC:
         return 4
@@ -195,16 +214,35 @@ def memory_limited_in_flight(images, wanted, K, D, base_channel, num_layers, bat
     if not images:
         return wanted
     dev = images[0].device
-    need = max(fit_bytes(*tuple(t.shape), K, D, base_channel, num_layers, batch_size, epochs, cfg) for t in images)
+    Ks = k_per_fit(K, len(images))
+    need = max(fit_bytes(*tuple(t.shape), k, D, base_channel, num_layers, batch_size, epochs, cfg) for t, k in zip(images, Ks))
+    shared = max(image_bytes(*tuple(t.shape)) for t in images)
     free, total = torch.cuda.mem_get_info(dev)
     free += torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)     # cached blocks are this process's to reuse
     if device_shared():
         free //= 2                                                                  # (the neighbour process sizes itself the same way)
-    fits = int(0.85 * free // need)
+    # (what has no device pointer -- a stand-in that only names a shape -- is an image of its own)
+    keys = [t.data_ptr() if hasattr(t, "data_ptr") else ("entry", k) for k, t in enumerate(images)]
+    fits = in_flight_that_fit(keys, need, shared, 0.85 * free, wanted)
     if fits < 1:
         raise ops._lib.LbdrnError(f"one fit of this shape holds {need / 2**30:.1f} GiB on the device, {free / 2**30:.1f} GiB are free "
                                   f"(of {total / 2**30:.0f}): split the image (-sr)")
     return max(1, min(wanted, fits))
+
+
+def in_flight_that_fit(image_keys, need, shared, budget, wanted):
+    """The largest m <= max(wanted, 1) for which m fits in flight hold at most `budget` bytes (0: not even one).  need: the
+    bytes of one fit, its image included (fit_bytes); shared: the image's part of that (image_bytes); image_keys: what
+    tells the images apart, in fit order (the device pointers).  The same device tensor passed several times -- one raster
+    at several K -- is ONE image, counted once; the MSB plane, the row matrix and the workspaces are every fit's own.
+    Fits go in flight in input order (fit_many), so the m that matter are runs of m consecutive entries: the run with
+    the most distinct images decides.  With every image distinct this is budget // need."""
+    for m in range(max(int(wanted), 1), 0, -1):
+        run = min(m, len(image_keys))      # (more wanted than there are fits: held to the same sum, as before)
+        distinct = max(len(set(image_keys[k:k + run])) for k in range(len(image_keys) - run + 1)) + m - run
+        if m * (need - shared) + distinct * shared <= budget:
+            return m
+    return 0
 
 
 # What the two launches that share the chip during a lone fit's background evaluation pass achieve, as fractions of the
@@ -310,7 +348,7 @@ def fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
             draws = draw_fit(geom.F, base_channel, C, num_layers, epochs, val_duration)
     stream = DevicePermutationStream(N, epochs, val_duration, dev, train_seeds=draws.train_seeds)
     net = ops.make_net(geom.F, base_channel, C, num_layers, cfg.act)
-    params = draws.params.to(dev).contiguous()
+    params = draws.params.to(dev, copy=True).contiguous()      # (its own copy: the draws may serve other fits)
     if params.numel() != ops.param_count(net):
         raise ValueError("draws were made for another network shape")
     draws_params0 = params.clone()
@@ -404,9 +442,16 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
     the whole chip, where two independent chains of 128-workgroup launches only meet by chance.  Each fit is exactly
     fit_device()'s fit (same draws, same kernels per fit, own workspace and state): the results are bit-identical to
     fitting the images one after another.  `seed`: every fit seeds the generator itself (independent images, one
-    encode.py invocation each); `draws`: one FitDraws per image.  Returns one DeviceFit per image."""
+    encode.py invocation each); `draws`: one FitDraws per image.  Returns one DeviceFit per image.
+    K: one int, or one K per image -- the K points of one raster's sweep are such a group: imgs_d may then hold the same
+    tensor several times, and draws the same FitDraws (every point of a sweep re-seeds: ref encode.py:200-205; a
+    FitDraws is only read here).  Fits that bring the same training seeds share ONE permutation stream: each epoch's
+    permutation is generated once and the same device tensor is handed to all of them (lbdrn_hip.h: perm entries may
+    alias, nothing writes through them).  The MSB plane, msb_max, the row matrix, the workspaces and the evaluation
+    pass (whether it qualifies for LBDRN_EVAL_X16 depends on that fit's msb_max) are every fit's own."""
     cfg = cfg or FeatCfg.from_constants()
     G = len(imgs_d)
+    Ks = k_per_fit(K, G)
     dev = imgs_d[0].device
     C, H, W = imgs_d[0].shape
     if any(tuple(t.shape) != (C, H, W) for t in imgs_d):
@@ -417,7 +462,8 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
     outs = [DeviceFit() for _ in range(G)]
     st = []
     net = None
-    for k, img_d in enumerate(imgs_d):
+    streams = {}     # training seeds -> the permutation stream of the fits that bring them
+    for k, (img_d, K) in enumerate(zip(imgs_d, Ks)):
         msb_d, msb_max = ops.split_bits(img_d, K)            # a1
         geom = ops.FeatureGeometry(C, H, W, K, D, msb_max, cfg, dev)
         dr = draws[k] if draws is not None else None
@@ -427,14 +473,17 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
                     torch.manual_seed(seed)
                 dr = draw_fit(geom.F, base_channel, C, num_layers, epochs, val_duration)
         net = ops.make_net(geom.F, base_channel, C, num_layers, cfg.act)
-        params = dr.params.to(dev).contiguous()
+        params = dr.params.to(dev, copy=True).contiguous()      # (its own copy: the draws may serve other fits)
         if params.numel() != ops.param_count(net):
             raise ValueError("draws were made for another network shape")
         steps = (N + batch_size - 1) // batch_size
+        seeds = tuple(int(s_) for s_ in dr.train_seeds)
+        if seeds not in streams:
+            streams[seeds] = DevicePermutationStream(N, epochs, val_duration, dev, train_seeds=seeds)
         st.append(dict(
             img=img_d, msb=msb_d, msb_max=msb_max, geom=geom, params=params, params0=params.clone(),
             m=torch.zeros_like(params), v=torch.zeros_like(params),
-            perms=DevicePermutationStream(N, epochs, val_duration, dev, train_seeds=dr.train_seeds),
+            perms=streams[seeds],
             losses=torch.zeros((epochs, steps), dtype=torch.float32, device=dev) if keep_losses else None,
             tws=ops.TrainWorkspace(geom, net, batch_size, dev).prepare(img_d, msb_d, path),   # a2-a4
             aws=ops.ApplyWorkspace(geom, net, dev)))
@@ -446,7 +495,8 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
         f["mses"] = torch.zeros((max(len(eval_epochs), 1),), dtype=torch.float32, device=dev)
     adam_steps = 0
     for e in range(1, epochs + 1):
-        perms = [f["perms"].get(e).to(dev, non_blocking=True) for f in st]          # a4
+        of_stream = {id(ps): ps.get(e).to(dev, non_blocking=True) for ps in streams.values()}          # a4
+        perms = [of_stream[id(f["perms"])] for f in st]
         ops.train_epoch_group([f["geom"] for f in st], net, [f["img"] for f in st], [f["msb"] for f in st], perms,
                               batch_size, [f["params"] for f in st], [f["m"] for f in st], [f["v"] for f in st],
                               adam_steps, lrs[e - 1], [f["losses"][e - 1] for f in st] if keep_losses else None,
@@ -470,9 +520,10 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
             best_mse = torch.where(improved, mse, best_mse)
             mse_log[e - 1, 0] = mse[0]
             mse_log[e - 1, 1] = improved[0].float()
-        f["perms"].close()
         out.best_params, out.msb, out.msb_max, out.geom, out.net = best_params, f["msb"], f["msb_max"], f["geom"], net
         out.mse_log, out.losses, out.epochs = mse_log, f["losses"], epochs
+    for ps in streams.values():
+        ps.close()
     return outs
 
 
@@ -498,10 +549,16 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
     results are bit-identical to fitting them one after another, whatever the grouping.
     `then(fit)` runs on the worker's stream right after its fit (weight truncation + reconstruction, payload
     coding, ...).  `draws`: one FitDraws per image instead of `seed` (the tiles of one image, whose draws the
-    caller made in tile order).  Returns after all streams have been joined to the caller's current stream."""
+    caller made in tile order).  Returns after all streams have been joined to the caller's current stream.
+    K: one int, or one K per image.  With a list, `images` may name one device tensor several times (the K points of one
+    raster: counted once against the free memory) and `draws` one FitDraws several times (read-only); consecutive
+    entries of one raster shape form a group whatever their K, and a group whose fits bring the same training seeds
+    generates each permutation once (fit_group)."""
+    Ks = k_per_fit(K, len(images))
+    K = Ks[0] if Ks else K
     if in_flight is None:
         in_flight = default_in_flight(*tuple(images[0].shape), K, D, base_channel, num_layers, cfg, path) if images else 4
-    in_flight = memory_limited_in_flight(images, in_flight, K, D, base_channel, num_layers, batch_size, epochs, cfg)
+    in_flight = memory_limited_in_flight(images, in_flight, Ks, D, base_channel, num_layers, batch_size, epochs, cfg)
     if group is None:
         group = int(os.environ.get("LBDRN_FIT_GROUP", "0"))
         if group == 0:
@@ -524,7 +581,7 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
     taken = []   # worker index -> stream of the process-wide pool
 
     def work(job):
-        idx, imgs, drs = job
+        idx, imgs, drs, ks = job
         if not hasattr(local, "stream"):
             # streams are kept for the life of the process: torch's caching allocator pools memory per stream,
             # so a fresh stream per call would send every fit's 3.5 GB workspace back to hipMalloc
@@ -535,10 +592,10 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
             local.stream.wait_stream(caller)
         with torch.cuda.stream(local.stream):
             if len(imgs) == 1:
-                fits = [fit_device(imgs[0], K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg,
+                fits = [fit_device(imgs[0], ks[0], D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg,
                                    path, seed=seed, draws=drs[0], alone=False)]
             else:
-                fits = fit_group(imgs, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
+                fits = fit_group(imgs, ks, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
                                  seed=seed, draws=drs if draws is not None else None)
             outs = [then(fit) if then is not None else fit for fit in fits]
             done = torch.cuda.Event()
@@ -548,26 +605,16 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
     drs_all = draws if draws is not None else [None] * len(images)
     if in_flight <= 1 or len(images) <= 1:
         results = []
-        for img_d, dr in zip(images, drs_all):
-            fit = fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
+        for img_d, dr, k_ in zip(images, drs_all, Ks):
+            fit = fit_device(img_d, k_, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
                              seed=seed, draws=dr)
             results.append(then(fit) if then is not None else fit)
         return results
-    # consecutive images of one shape, `group` at a time
-    def form(group):
-        jobs, k = [], 0
-        while k < len(images):
-            n = 1
-            while n < group and k + n < len(images) and tuple(images[k + n].shape) == tuple(images[k].shape):
-                n += 1
-            jobs.append((list(range(k, k + n)), list(images[k:k + n]), list(drs_all[k:k + n])))
-            k += n
-        return jobs
-    jobs = form(group)
+    jobs = form_jobs(images, drs_all, Ks, group)
     if group > 1 and 2 * sum(len(j[0]) for j in jobs if len(j[0]) > 1) < len(images):
         # mostly odd ones out (tiles of many shapes): groups would only halve the number of chains
         group = 1
-        jobs = form(1)
+        jobs = form_jobs(images, drs_all, Ks, 1)
     with ThreadPoolExecutor(max_workers=max(1, in_flight // group)) as pool:
         done_jobs = list(pool.map(work, jobs))
     results = [None] * len(images)
@@ -576,6 +623,19 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
         for i, o in zip(idx, outs):
             results[i] = o
     return results
+
+
+def form_jobs(images, draws, Ks, group):
+    """fit_many's jobs: consecutive images of one raster shape, `group` at a time, whatever their K (the group call takes
+    what differs between the K points of a raster; a shape change splits) -> [(indices, images, draws, Ks), ...]."""
+    jobs, k = [], 0
+    while k < len(images):
+        n = 1
+        while n < group and k + n < len(images) and tuple(images[k + n].shape) == tuple(images[k].shape):
+            n += 1
+        jobs.append((list(range(k, k + n)), list(images[k:k + n]), list(draws[k:k + n]), list(Ks[k:k + n])))
+        k += n
+    return jobs
 
 
 def truncate_device(params, precision):
@@ -642,20 +702,35 @@ def fit_image(img, K, D, base_channel, num_layers, lr, batch_size, epochs, val_d
 
 
 def fit_images(imgs, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration=1, cfg=None,
-               device="cuda:0", path=ops.PATH_AUTO, host_msb=True, draws=None, seed=None, in_flight=None):
+               device="cuda:0", path=ops.PATH_AUTO, host_msb=True, draws=None, seed=None, in_flight=None, errors="raise"):
     """fit_image for several rasters with `in_flight` of them progressing at a time on the GPU (fit_many).
     Either every fit seeds itself (`seed`: independent images, one encode.py invocation each in the reference)
-    or the caller brings the draws it made in order (`draws`: the tiles of one image, ref encode.py:231-262)."""
+    or the caller brings the draws it made in order (`draws`: the tiles of one image, ref encode.py:231-262).
+    K: one int, or one per entry; an array that appears several times in `imgs` (one tile at several K) is uploaded once.
+    errors="return": a fit whose result cannot be taken to the host (_host_result: no epoch improved) is that entry's
+    exception in the list instead of ending the call -- the other points of a sweep finish."""
     t0 = time.time()
     dev = torch.device(device)
-    tiles = [ops.to_device_u16(_as_planes(img), dev) for img in imgs]
+    uploaded = {}
+    for img in imgs:
+        if id(img) not in uploaded:
+            uploaded[id(img)] = ops.to_device_u16(_as_planes(img), dev)
+    tiles = [uploaded[id(img)] for img in imgs]
     t1 = time.time()
     fits = fit_many(tiles, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
                     seed=seed, in_flight=in_flight, draws=draws)
-    results = [_host_result(fit, epochs, {"upload": (t1 - t0) / max(len(imgs), 1)}, host_msb) for fit in fits]
+    results = []
+    for fit in fits:
+        try:
+            results.append(_host_result(fit, epochs, {"upload": (t1 - t0) / max(len(imgs), 1)}, host_msb))
+        except Exception as e:
+            if errors != "return":
+                raise
+            results.append(e)
     per_tile = (time.time() - t1) / max(len(imgs), 1)
     for res in results:
-        res.seconds["fit"] = per_tile          # wall time per tile with the others in flight
+        if not isinstance(res, Exception):
+            res.seconds["fit"] = per_tile          # wall time per tile with the others in flight
     return results
 
 

@@ -213,8 +213,15 @@ class TrainWorkspace:
         img, msb = _u16(img.contiguous()), _u16(msb.contiguous())
         _call(lib().lbdrn_train_prepare, img, ctypes.byref(self.geom.c), ctypes.byref(self.net), _ptr(img),
                                         _ptr(msb), self.batch_size, _ptr(self.buf), self.nbytes, path)
-        self.prepared_for = (img.data_ptr(), path)
+        self.prepared_for = self.key(img, path, self.geom)
         return self
+
+    @staticmethod
+    def key(img, path, geom):
+        """What a prepared workspace holds the rows and labels OF: the image, the path, and what the row build reads of
+        the geometry besides the raster shape -- K (the label mask), D (the window) and msb_max (the divisor).  One image
+        fitted at several K has one workspace per K (codec.fit_group with a K list)."""
+        return (img.data_ptr(), path, int(geom.c.K), int(geom.c.D), int(geom.c.msb_max))
 
 
 def train_epoch(geom, net, img, msb, perm, batch_size, params, exp_avg, exp_avg_sq, adam_step0, lr,
@@ -229,7 +236,7 @@ def train_epoch(geom, net, img, msb, perm, batch_size, params, exp_avg, exp_avg_
         assert t.dtype == torch.float32 and t.is_contiguous()
     if ws is None:
         ws = TrainWorkspace(geom, net, batch_size, img.device).prepare(img, msb, path)
-    if ws.prepared_for != (img.data_ptr(), path):
+    if ws.prepared_for != TrainWorkspace.key(img, path, geom):
         raise _lib.LbdrnError("TrainWorkspace.prepare(img, msb, path) must run once for this image first")
     _call(lib().lbdrn_train_epoch, img, ctypes.byref(geom.c), ctypes.byref(net), _ptr(img), _ptr(msb),
                                   _ptr(perm), perm.numel(), batch_size, _ptr(params), _ptr(exp_avg),
@@ -258,7 +265,9 @@ def train_epoch_group(geoms, net, imgs, msbs, perms, batch_size, params, exp_avg
                       losses=None, path=PATH_AUTO, wss=None):
     """train_epoch for several independent fits of ONE shape, stepping side by side (lbdrn_train_epoch_group: one
     launch per minibatch for the whole group where the fused step takes groups).  Lists, one entry per fit; every
-    workspace prepared for its image.  Same numbers as one train_epoch call per fit."""
+    workspace prepared for its image and geometry.  K and msb_max may differ from fit to fit, images and permutations
+    may be one tensor handed over several times (the K points of one image).  Same numbers as one train_epoch call
+    per fit."""
     n = len(imgs)
     _need_cuda(*imgs, *msbs, *perms, *params, *exp_avgs, *exp_avg_sqs)
     imgs = [_u16(t.contiguous()) for t in imgs]
@@ -267,8 +276,8 @@ def train_epoch_group(geoms, net, imgs, msbs, perms, batch_size, params, exp_avg
         assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == perms[0].numel()
     for t in list(params) + list(exp_avgs) + list(exp_avg_sqs):
         assert t.dtype == torch.float32 and t.is_contiguous()
-    for ws, img in zip(wss, imgs):
-        if ws.prepared_for != (img.data_ptr(), path) or ws.nbytes != wss[0].nbytes:
+    for ws, img, geom in zip(wss, imgs, geoms):
+        if ws.prepared_for != TrainWorkspace.key(img, path, geom) or ws.nbytes != wss[0].nbytes:
             raise _lib.LbdrnError("every fit of a group needs its own TrainWorkspace, prepared for its image")
     arr = lambda ptrs: (ctypes.c_void_p * n)(*ptrs)
     garr = (ctypes.POINTER(Geom) * n)(*[ctypes.pointer(g.c) for g in geoms])

@@ -14,6 +14,9 @@ HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")" && pwd)"
 if [ -z "${NGPU}" ] && [[ "$1" =~ ^[0-9]+$ ]]; then
     export HIP_VISIBLE_DEVICES="$1"
 fi
+# K_IN_FLIGHT=N (default: unset = 1) is sweep.py's --k-in-flight N: a process fits up to N of the K points of an image side by
+# side instead of one after another (same files; meant for PER_GPU=1, where a lone fit leaves half of the chip idle).
+if [ -n "${K_IN_FLIGHT}" ]; then set -- "$@" --k-in-flight "${K_IN_FLIGHT}"; fi
 NPROC=$(( ${NGPU:-1} * ${PER_GPU:-2} ))
 if [ "${PER_GPU:-2}" -gt 1 ]; then export LBDRN_DEVICE_SHARED="${LBDRN_DEVICE_SHARED:-1}" LBDRN_OVERLAP_EVAL="${LBDRN_OVERLAP_EVAL:-0}"; fi
 if [ "${NPROC}" -gt 1 ]; then

@@ -10,6 +10,10 @@ results_summary.py.
     python -m torch.distributed.run --nproc-per-node 8 sweep.py -o outputs --images data/*.tif
     python sweep.py -o outputs --images a.tif b.tif --k 1 6            # single GPU
 
+--k-in-flight N (default 1: the loop above, point after point): a rank fits up to N of the K points it was dealt of one
+image side by side on its GPU (encode.main_k_points -- one raster, one set of draws, one launch per minibatch for a pair
+of K's) and then decodes them one after another; files, records and the CSV are those of the default.
+
 The positional form of run.sh is kept too:  sweep.py DEVICE_ID D BC NL LR BS EPOCH SR OUTPUT_DIR
 (run.sh exports HIP_VISIBLE_DEVICES=DEVICE_ID unless NGPU is set; sweep.py itself takes its device from the launcher).
 """
@@ -45,6 +49,9 @@ def build_parser():
     p.add_argument("-bs", "--batch_size", type=int, default=8192)
     p.add_argument("-e", "--epochs", type=int, default=10)
     p.add_argument("--summary", action="store_true", help="rank 0 writes the results CSV at the end")
+    p.add_argument("--k-in-flight", dest="k_in_flight", type=int, default=1, metavar="N",
+                   help="fit up to N of the K points of an image side by side on the GPU (encode.main_k_points); "
+                        "default 1: point after point.  Same files and records either way")
     return p
 
 
@@ -57,6 +64,8 @@ def parse(argv=None):
         a.D, a.base_channel, a.num_layers, a.lr = int(D), int(BC), int(NL), LR
         a.batch_size, a.epochs, a.split_ratio, a.output_dir = int(BS), int(EPOCH), int(SR), OUT
     a.images = a.images if a.images else list(REFERENCE_IMAGES)
+    if a.k_in_flight < 1:
+        raise SystemExit(f"--k-in-flight {a.k_in_flight}: 1 (point after point) or more")
     if os.environ.get("LBDRN_WEIGHTS_CODEC") != "fpzip":
         from lbdrn_hip import container
         try:   # before any fit of the sweep starts
@@ -71,17 +80,71 @@ def points(a):
     return [(img, K) for img in a.images for K in range(a.k[0], a.k[1] + 1)]
 
 
-def run_point(a, image, K):
-    stem = os.path.splitext(os.path.basename(image))[0]
-    common = ["-K", str(K), "-D", str(a.D), "-bc", str(a.base_channel), "-nl", str(a.num_layers),
-              "-lr", a.lr, "-bs", str(a.batch_size), "-e", str(a.epochs), "-sr", str(a.split_ratio),
-              "-prec", str(a.precision)]
-    encode.main(["-i", image, "-o", a.output_dir] + common, shard_tiles=False)
+def common_args(a):
+    return ["-D", str(a.D), "-bc", str(a.base_channel), "-nl", str(a.num_layers),
+            "-lr", a.lr, "-bs", str(a.batch_size), "-e", str(a.epochs), "-sr", str(a.split_ratio),
+            "-prec", str(a.precision)]
+
+
+def point_folder(a, image, K):
     # float(lr) -> the directory name encode.py derives from its parsed float (ref run.sh:38 spells it by hand)
-    folder = (f"{a.output_dir}/{stem}_r{a.split_ratio}_K{K}_bc{a.base_channel}_nl{a.num_layers}_D{a.D}"
-              f"_prec{a.precision}_lr{float(a.lr)}_bs{a.batch_size}_e{a.epochs}")
+    stem = os.path.splitext(os.path.basename(image))[0]
+    return (f"{a.output_dir}/{stem}_r{a.split_ratio}_K{K}_bc{a.base_channel}_nl{a.num_layers}_D{a.D}"
+            f"_prec{a.precision}_lr{float(a.lr)}_bs{a.batch_size}_e{a.epochs}")
+
+
+def decode_point(a, image, K):
+    stem = os.path.splitext(os.path.basename(image))[0]
+    folder = point_folder(a, image, K)
     decode.main(["-i", f"{folder}/{stem}.bin", "-org", image], shard_tiles=False)
     return folder
+
+
+def run_point(a, image, K):
+    encode.main(["-i", image, "-o", a.output_dir, "-K", str(K)] + common_args(a), shard_tiles=False)
+    return decode_point(a, image, K)
+
+
+def buckets(todo, mine, k_in_flight):
+    """The points a rank was dealt (`mine`: indices into `todo`, ascending = run.sh's order), bucketed by image: up to
+    k_in_flight points of one image each, in that order -> [[index, ...], ...].  Dealing over the ranks stays per
+    point; a rank that holds K = 1, 3, 5 of an image fits those three together."""
+    by_image = {}
+    for idx in mine:
+        by_image.setdefault(todo[idx][0], []).append(idx)
+    out = []
+    for idxs in by_image.values():
+        out += [idxs[k:k + k_in_flight] for k in range(0, len(idxs), k_in_flight)]
+    return out
+
+
+def run_bucket(a, rank, todo, idxs):
+    """Encode the K points todo[idxs] of one image together (encode.main_k_points), then decode them one after another
+    as run_point does -> one record per point, in idxs order.  A point's seconds: its share of the encode all of them
+    did together, plus its own decode."""
+    image = todo[idxs[0]][0]
+    Ks = [todo[idx][1] for idx in idxs]
+    t0 = time.time()
+    for K in Ks:
+        print(f"[rank {rank}] Processing file: {image}  K={K}", flush=True)
+    try:
+        outcome = encode.main_k_points(["-i", image, "-o", a.output_dir] + common_args(a), Ks)
+    except Exception as e:
+        outcome = {K: e for K in Ks}
+    share = (time.time() - t0) / len(Ks)
+    records = []
+    for idx, K in zip(idxs, Ks):
+        t1 = time.time()
+        folder, e = None, outcome.get(K)
+        if e is None:
+            try:
+                folder = decode_point(a, image, K)
+            except Exception as e_:
+                e = e_
+        if e is not None:      # run.sh carries on after a failed point; so does the sweep
+            traceback.print_exception(type(e), e, e.__traceback__)
+        records.append((idx, image, K, folder, None if e is None else f"{type(e).__name__}: {e}", share + time.time() - t1))
+    return records
 
 
 def main(argv=None):
@@ -90,7 +153,13 @@ def main(argv=None):
     encode.DEVICE = decode.DEVICE = shard.bind_device(local)
     todo = points(a)
     records = []
-    for idx in shard.assign(len(todo), rank, world):
+    mine = shard.assign(len(todo), rank, world)
+    if a.k_in_flight > 1:
+        for idxs in buckets(todo, mine, a.k_in_flight):
+            records += run_bucket(a, rank, todo, idxs)
+        records.sort()      # (run.sh's order, like the loop below)
+        mine = []
+    for idx in mine:
         image, K = todo[idx]
         t0 = time.time()
         print(f"[rank {rank}] Processing file: {image}  K={K}", flush=True)
