@@ -1,4 +1,4 @@
-"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so and liblbdrn_resid.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so and liblbdrn_tiff.so for gfx950 with hipcc (in-tree, next to the Python host code).
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -91,6 +91,29 @@ def build_resid(force=False):
     return RESID_OUT
 
 
+TIFF_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_tiff.so")
+TIFF_SRCS = ["tiff.hip"]
+TIFF_DEPS = ["tiff.inc", "common.hpp", "exports_tiff.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_tiff.h"]
+
+
+def build_tiff(force=False):
+    """liblbdrn_tiff.so (include/lbdrn_tiff.h): the TIFF reader's segment decoders and placement, a library of its own
+    like liblbdrn_resid.so -- same compiler, same flags, its own object file and version script."""
+    if not force and os.path.exists(TIFF_OUT):
+        t = os.path.getmtime(TIFF_OUT)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in TIFF_SRCS + TIFF_DEPS + ["build.py"]):
+            return TIFF_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = []
+    for src in TIFF_SRCS:
+        obj = os.path.join(HERE, src.replace(".hip", ".o"))
+        objs.append(obj)
+        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
+                           "-Wl,--version-script=" + os.path.join(HERE, "exports_tiff.map"), "-o", TIFF_OUT] + objs)
+    return TIFF_OUT
+
+
 def stale():
     if not os.path.exists(OUT):
         return True
@@ -103,6 +126,7 @@ def build(force=False, extra=(), out=None):
     if out == OUT:
         build_jp2k_dec(force)
         build_resid(force)
+        build_tiff(force)
     if out == OUT and not force and not stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -135,4 +159,5 @@ if __name__ == "__main__":
         print(build(force="--force" in sys.argv))
         print(JP2K_DEC_OUT)
         print(RESID_OUT)
+        print(TIFF_OUT)
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

@@ -2,8 +2,10 @@
 
 GDAL is used when it is importable.  Without it this module reads and writes the subset the codec
 itself produces and consumes: baseline TIFF, uncompressed strips, unsigned 8/16-bit or float32
-samples, any band count, chunky or planar, either byte order -- and .npy arrays.  Arrays are
-[C,H,W] (or [H,W] for one band), as gdal's ReadAsArray() returns them.
+samples, any band count, chunky or planar, either byte order -- and .npy arrays.  Every other TIFF
+-- BigTIFF, tiles, LZW / Deflate / PackBits, predictor 2 -- goes to lbdrn_hip.tiff, which parses it on
+the host and decompresses its segments on the GPU.  Arrays are [C,H,W] (or [H,W] for one band), as
+gdal's ReadAsArray() returns them.
 """
 import struct
 
@@ -30,6 +32,29 @@ def read_raster(path):
     return _read_tiff(path)
 
 
+def read_raster_device(path, device="cuda:0"):
+    """The raster as a contiguous [C,H,W] tensor on `device`, for callers that want the planes left in HBM: 16-bit samples as
+    int16 storage, like every plane of this package.  A tiled or compressed TIFF never passes through host arrays."""
+    import torch
+    a = None
+    if path.endswith(".npy") or _gdal() is not None:
+        a = read_raster(path)
+    else:
+        from . import tiff
+        with open(path, "rb") as f:
+            buf = f.read()
+        try:
+            scene = tiff.parse(buf, path)
+        except ValueError:
+            scene = None      # float samples and the like: this module's own reader takes them or says why not
+        if scene is None or (scene.plain_strips() and buf[2:4] in (b"*\0", b"\0*")):
+            a = _read_tiff(path)
+        else:
+            return tiff.read_device_bytes(buf, path, device)
+    a = np.ascontiguousarray(a if a.ndim == 3 else a[None])
+    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)
+
+
 def write_raster(path, array):
     """array [C,H,W]: uint8 / uint16 / float32 / float64 (ref write_tiff_with_gdal)."""
     if array.dtype.type not in (np.uint8, np.uint16, np.float32, np.float64):
@@ -54,12 +79,18 @@ def raster_size(path):
     return a.shape[-1], a.shape[-2]
 
 
+def _read_tiff_device(path):
+    """what _read_tiff does not read by itself: parsed on the host, decompressed on the GPU (lbdrn_hip/tiff.py)"""
+    from . import tiff
+    return tiff.read(path)
+
+
 def _read_tiff(path):
     with open(path, "rb") as f:
         buf = f.read()
     bo = {b"II": "<", b"MM": ">"}.get(buf[:2])
     if bo is None or struct.unpack_from(bo + "H", buf, 2)[0] != 42:
-        raise ValueError(f"{path}: not a classic TIFF (BigTIFF and other containers need GDAL)")
+        return _read_tiff_device(path)      # BigTIFF; anything that is no TIFF at all raises there
     off = struct.unpack_from(bo + "I", buf, 4)[0]
     n = struct.unpack_from(bo + "H", buf, off)[0]
     tags = {}
@@ -79,9 +110,9 @@ def _read_tiff(path):
     bits = tags.get(258, [1])
     spp = tags.get(277, [1])[0]
     if tags.get(259, [1])[0] != 1:
-        raise ValueError(f"{path}: compressed TIFF needs GDAL")
+        return _read_tiff_device(path)
     if 322 in tags:
-        raise ValueError(f"{path}: tiled TIFF needs GDAL")
+        return _read_tiff_device(path)
     fmt = tags.get(339, [1])[0]
     planar = tags.get(284, [1])[0]
     if len(set(bits)) != 1:

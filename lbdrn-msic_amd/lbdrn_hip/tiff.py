@@ -1,0 +1,331 @@
+"""TIFF scenes that raster_io's own reader refuses -- tiled, LZW / Deflate / PackBits compressed, predictor 2, BigTIFF --
+parsed on the host and decompressed on the GPU: the ctypes binding of liblbdrn_tiff.so (include/lbdrn_tiff.h,
+csrc/tiff.hip, csrc/tiff.inc).  Built by csrc/build.py beside liblbdrn_hip.so; LBDRN_TIFF_LIB names another file.
+
+    parse(buf)                 the first IFD of a classic TIFF or BigTIFF, either byte order -> Scene (layout + segment table)
+    read_device(path, device)  contiguous [C,H,W] tensor in HBM: int16 storage for 16-bit samples, like every plane of this
+                               package, uint8 for 8-bit ones
+    read(path, device)         numpy, with the conventions of raster_io._read_tiff ([H,W] for one band)
+
+Everything outside the subset raises ValueError naming the tag and value before any device work.  Georeferencing tags are
+ignored, as the reference's own writer drops them."""
+import ctypes
+import os
+import struct
+import zlib
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_PATH = os.environ.get("LBDRN_TIFF_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_tiff.so")
+ABI_VERSION = 1
+E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
+COMP_NONE, COMP_LZW, COMP_DEFLATE, COMP_DEFLATE_OLD, COMP_PACKBITS = 1, 5, 8, 32946, 32773
+STATUS_TEXT = {1: "the stream ends before the segment is complete", 2: "invalid code", 3: "a match distance points before the segment",
+               4: "bad zlib header", 5: "wrong Adler-32"}
+
+_lib = None
+
+
+class TiffError(RuntimeError):
+    def __init__(self, message, status=None):
+        super().__init__(message)
+        self.status = status
+
+
+class Layout(ctypes.Structure):
+    """lbdrn_tiff_layout"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("C", "H", "W", "bits", "big_endian", "planar", "seg_w", "seg_h", "tiled",
+                                              "compression", "predictor")]
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(_PATH):
+            raise TiffError(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
+        L = ctypes.CDLL(_PATH)
+        vp, sz = ctypes.c_void_p, ctypes.c_size_t
+        lp = ctypes.POINTER(Layout)
+        L.lbdrn_tiff_last_error.restype = ctypes.c_char_p
+        L.lbdrn_tiff_abi_version.restype = ctypes.c_int
+        L.lbdrn_tiff_segment_count.argtypes = [lp]
+        L.lbdrn_tiff_segment_count.restype = sz
+        L.lbdrn_tiff_segment_cap.argtypes = [ctypes.c_int32]
+        L.lbdrn_tiff_segment_cap.restype = sz
+        L.lbdrn_tiff_workspace.argtypes = [lp]
+        L.lbdrn_tiff_workspace.restype = sz
+        L.lbdrn_tiff_decode.argtypes = [lp, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp]
+        if L.lbdrn_tiff_abi_version() != ABI_VERSION:
+            raise TiffError(f"{_PATH}: ABI version {L.lbdrn_tiff_abi_version()}, this binding is for {ABI_VERSION}")
+        _lib = L
+    return _lib
+
+
+def available():
+    try:
+        lib()
+        return True
+    except (TiffError, OSError):
+        return False
+
+
+def _check(rc, what):
+    if rc != 0:
+        raise TiffError(f"{what}: {(lib().lbdrn_tiff_last_error() or b'').decode(errors='replace')}", rc)
+
+
+# ---------------------------------------------------------------- the parser
+
+# type -> (struct code, bytes); 16-18 are BigTIFF's LONG8, SLONG8, IFD8
+_FIELD = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2), 9: ("i", 4),
+          10: ("ii", 8), 11: ("f", 4), 12: ("d", 8), 13: ("I", 4), 16: ("Q", 8), 17: ("q", 8), 18: ("Q", 8)}
+_WANTED = {256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression", 273: "StripOffsets",
+           277: "SamplesPerPixel", 278: "RowsPerStrip", 279: "StripByteCounts", 284: "PlanarConfiguration", 317: "Predictor",
+           322: "TileWidth", 323: "TileLength", 324: "TileOffsets", 325: "TileByteCounts", 338: "ExtraSamples", 339: "SampleFormat"}
+
+
+class Scene:
+    """what parse() returns: the layout the library takes, the segment table, and the sample format for the host paths"""
+
+    def __init__(self, layout, offsets, counts, sample_format, byteorder):
+        self.layout, self.offsets, self.counts = layout, offsets, counts
+        self.sample_format, self.byteorder = sample_format, byteorder
+
+    @property
+    def shape(self):
+        return self.layout.C, self.layout.H, self.layout.W
+
+    def plain_strips(self):
+        """the subset raster_io._read_tiff reads by itself"""
+        return self.layout.compression == COMP_NONE and not self.layout.tiled
+
+
+def read_tags(buf, path="TIFF"):
+    """{tag: [values]} of the first IFD, the byte order mark ('<' or '>') and whether the file is a BigTIFF"""
+    bo = {b"II": "<", b"MM": ">"}.get(bytes(buf[:2]))
+    if bo is None or len(buf) < 8:
+        raise ValueError(f"{path}: not a TIFF (no II / MM byte order mark)")
+    magic = struct.unpack_from(bo + "H", buf, 2)[0]
+    if magic == 42:
+        big = False
+        off = struct.unpack_from(bo + "I", buf, 4)[0]
+    elif magic == 43:
+        big = True
+        if len(buf) < 16 or struct.unpack_from(bo + "HH", buf, 4) != (8, 0):
+            raise ValueError(f"{path}: BigTIFF header with an offset size other than 8")
+        off = struct.unpack_from(bo + "Q", buf, 8)[0]
+    else:
+        raise ValueError(f"{path}: not a TIFF (magic {magic})")
+    cnt_fmt, cnt_size, ent, inline = ("Q", 8, 20, 8) if big else ("H", 2, 12, 4)
+    if off + cnt_size > len(buf):
+        raise ValueError(f"{path}: the first IFD lies outside the file")
+    n = struct.unpack_from(bo + cnt_fmt, buf, off)[0]
+    if off + cnt_size + ent * n > len(buf):
+        raise ValueError(f"{path}: the first IFD lies outside the file")
+    tags = {}
+    for i in range(n):
+        at = off + cnt_size + ent * i
+        tag, typ = struct.unpack_from(bo + "HH", buf, at)
+        cnt = struct.unpack_from(bo + ("Q" if big else "I"), buf, at + 4)[0]
+        if tag not in _WANTED or typ not in _FIELD:
+            continue
+        code, size = _FIELD[typ]
+        if typ in (2, 5, 10, 11, 12):
+            raise ValueError(f"{path}: tag {tag} ({_WANTED[tag]}) has the non-integer type {typ}")
+        val_at = at + 4 + (8 if big else 4)
+        if size * cnt > inline:
+            val_at = struct.unpack_from(bo + ("Q" if big else "I"), buf, val_at)[0]
+        if val_at + size * cnt > len(buf):
+            raise ValueError(f"{path}: the values of tag {tag} ({_WANTED[tag]}) lie outside the file")
+        tags[tag] = np.frombuffer(buf, np.dtype(bo + {"B": "u1", "b": "i1", "H": "u2", "h": "i2", "I": "u4", "i": "i4", "Q": "u8",
+                                                    "q": "i8"}[code]), cnt, val_at).astype(np.int64 if code in "bhiq" else np.uint64).tolist()
+    return tags, bo, big
+
+
+def parse(buf, path="TIFF"):
+    """Scene of the first IFD; ValueError naming the tag and value for everything outside the subset."""
+    tags, bo, _ = read_tags(buf, path)
+
+    def one(tag, default=None):
+        v = tags.get(tag)
+        if v is None:
+            if default is None:
+                raise ValueError(f"{path}: tag {tag} ({_WANTED[tag]}) is missing")
+            return default
+        return int(v[0])
+    W, H = one(256), one(257)
+    C = one(277, 1)
+    bits = [int(b) for b in tags.get(258, [1])]
+    if len(bits) == 1 and C > 1:
+        bits = bits * C
+    comp = one(259, 1)
+    planar = one(284, 1)
+    # libtiff knows the predictor with LZW and Deflate only: with PackBits or no compression it writes the tag and stores the
+    # samples as they are, and ignores the tag when it reads.  So does this reader.
+    pred = one(317, 1) if comp in (COMP_LZW, COMP_DEFLATE, COMP_DEFLATE_OLD) else 1
+    fmt = [int(f) for f in tags.get(339, [1])]
+    if len(set(bits)) != 1 or len(bits) != C:
+        raise ValueError(f"{path}: BitsPerSample (258) = {bits}: mixed bit depths")
+    if len(set(fmt)) != 1:
+        raise ValueError(f"{path}: SampleFormat (339) = {fmt}: mixed sample formats")
+    if comp not in (COMP_NONE, COMP_LZW, COMP_DEFLATE, COMP_DEFLATE_OLD, COMP_PACKBITS):
+        raise ValueError(f"{path}: Compression (259) = {comp} is not read here (none, LZW 5, Deflate 8 / 32946, PackBits 32773 are)")
+    if pred not in (1, 2):
+        raise ValueError(f"{path}: Predictor (317) = {pred} is not read here (1 and 2 are)")
+    if planar not in (1, 2):
+        raise ValueError(f"{path}: PlanarConfiguration (284) = {planar}")
+    if fmt[0] != 1:
+        raise ValueError(f"{path}: SampleFormat (339) = {fmt[0]}: only unsigned integer samples are read from tiled or compressed files")
+    if bits[0] not in (8, 16):
+        raise ValueError(f"{path}: BitsPerSample (258) = {bits[0]}: only 8 and 16 bits are read from tiled or compressed files")
+    if not (1 <= W <= 1 << 20 and 1 <= H <= 1 << 20 and 1 <= C <= 65535):
+        raise ValueError(f"{path}: ImageWidth (256) x ImageLength (257) x SamplesPerPixel (277) = {W} x {H} x {C} is out of range")
+    tiled = 322 in tags or 324 in tags
+    if tiled:
+        sw, sh = one(322), one(323)
+        offsets, counts = tags.get(324), tags.get(325)
+        names = "TileOffsets (324) / TileByteCounts (325)"
+        if not (1 <= sw <= 1 << 20 and 1 <= sh <= 1 << 20):
+            raise ValueError(f"{path}: TileWidth (322) x TileLength (323) = {sw} x {sh} is out of range")
+    else:
+        sw, sh = W, min(max(one(278, 0xFFFFFFFF), 1), H)
+        offsets, counts = tags.get(273), tags.get(279)
+        names = "StripOffsets (273) / StripByteCounts (279)"
+    nseg = -(-W // sw) * -(-H // sh) * (C if planar == 2 else 1)
+    if offsets is None or counts is None or len(offsets) != nseg or len(counts) != nseg:
+        raise ValueError(f"{path}: {names}: {nseg} entries expected, {None if offsets is None else len(offsets)} / "
+                         f"{None if counts is None else len(counts)} found")
+    for i, (o, c) in enumerate(zip(offsets, counts)):
+        if o + c > len(buf):
+            raise ValueError(f"{path}: {names}: segment {i} (offset {o}, {c} bytes) lies outside the file's {len(buf)} bytes")
+    if comp == COMP_LZW:
+        for i, (o, c) in enumerate(zip(offsets, counts)):      # as libtiff detects the old bit order
+            if c >= 2 and buf[o] == 0 and (buf[o + 1] & 1):
+                raise ValueError(f"{path}: Compression (259) = 5: segment {i} is old-style (LSB-first) LZW, which is not read here")
+    lay = Layout(C, H, W, bits[0], 1 if bo == ">" else 0, planar, sw, sh, 1 if tiled else 0,
+                 COMP_DEFLATE if comp == COMP_DEFLATE_OLD else comp, pred)
+    return Scene(lay, np.asarray(offsets, np.uint64), np.asarray(counts, np.uint64), fmt[0], bo)
+
+
+# ---------------------------------------------------------------- the host path of an oversize Deflate segment
+
+def _segment_grid(lay):
+    per_row = -(-lay.W // lay.seg_w)
+    rows = -(-lay.H // lay.seg_h)
+    for b in (range(lay.C) if lay.planar == 2 else [None]):
+        for ty in range(rows):
+            for tx in range(per_row):
+                yield b, ty * lay.seg_h, tx * lay.seg_w
+
+
+def _read_host_deflate(buf, scene):
+    """zlib on the host, un-predicted and placed in numpy like raster_io's own reader: for a Deflate file whose writer put more
+    into one segment than the device decodes (a whole band in one strip)"""
+    lay = scene.layout
+    dt = np.dtype(scene.byteorder + ("u1" if lay.bits == 8 else "u2"))
+    native = dt.newbyteorder("=")
+    out = np.zeros((lay.C, lay.H, lay.W), native)
+    spp = 1 if lay.planar == 2 else lay.C
+    for i, (b, y0, x0) in enumerate(_segment_grid(lay)):
+        rows = min(lay.seg_h, lay.H - y0)
+        hh = lay.seg_h if lay.tiled else rows
+        o, c = int(scene.offsets[i]), int(scene.counts[i])
+        try:
+            raw = zlib.decompress(bytes(buf[o:o + c]))
+        except zlib.error as e:
+            raise TiffError(f"segment {i} is damaged: {e}") from None
+        if len(raw) < hh * lay.seg_w * spp * dt.itemsize:
+            raise TiffError(f"segment {i} is damaged: it holds {len(raw)} bytes of {hh * lay.seg_w * spp * dt.itemsize}")
+        seg = np.frombuffer(raw, dt, hh * lay.seg_w * spp).astype(native).reshape(hh, lay.seg_w, spp)
+        if lay.predictor == 2:
+            seg = np.cumsum(seg, axis=1, dtype=native)
+        cols = min(lay.seg_w, lay.W - x0)
+        dst = out[b:b + 1] if b is not None else out
+        dst[:, y0:y0 + rows, x0:x0 + cols] = seg[:rows, :cols, :].transpose(2, 0, 1)
+    return out
+
+
+def _segment_bytes(lay):
+    return lay.seg_w * lay.seg_h * (1 if lay.planar == 2 else lay.C) * (lay.bits // 8)
+
+
+def _over_cap(lay, path):
+    """None, 'host' (Deflate: the interpreter's zlib takes it) or a ValueError for a layout whose segments are above the cap"""
+    cap = lib().lbdrn_tiff_segment_cap(lay.compression)
+    if _segment_bytes(lay) <= cap:
+        return None
+    if lay.compression == COMP_DEFLATE:
+        return "host"
+    raise ValueError(f"{path}: a segment of {_segment_bytes(lay)} bytes is above the cap of {cap} bytes the device decodes for "
+                     f"Compression (259) = {lay.compression}, and there is no host decoder for it")
+
+
+# ---------------------------------------------------------------- entry points
+
+def _device(device):
+    import torch
+    dev = torch.device(device if device is not None else "cuda:0")
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise TiffError("a tiled or compressed TIFF is decompressed on the GPU; there is no CPU path in this package")
+    return dev
+
+
+def decode_device(buf, scene, dev):
+    """the planes of a parsed scene as a [C,H,W] tensor on dev; buf: the file's bytes"""
+    import torch
+    lay = scene.layout
+    L = lib()
+    nseg = L.lbdrn_tiff_segment_count(ctypes.byref(lay))
+    nws = L.lbdrn_tiff_workspace(ctypes.byref(lay))
+    if not nseg or nseg != len(scene.offsets):
+        raise TiffError("the layout is out of the library's range")
+    offsets = np.ascontiguousarray(scene.offsets, np.uint64)
+    counts = np.ascontiguousarray(scene.counts, np.uint64)
+    with torch.cuda.device(dev):
+        raw = torch.frombuffer(bytearray(buf), dtype=torch.uint8).to(dev)      # the file is uploaded once
+        planes = torch.empty((lay.C, lay.H, lay.W), dtype=torch.uint8 if lay.bits == 8 else torch.int16, device=dev)
+        status = torch.empty(nseg, dtype=torch.int32, device=dev)
+        ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
+        _check(L.lbdrn_tiff_decode(ctypes.byref(lay), raw.data_ptr(), raw.numel(), offsets.ctypes.data, counts.ctypes.data, nseg,
+                                   planes.data_ptr(), status.data_ptr(), ws.data_ptr(), nws,
+                                   torch.cuda.current_stream(dev).cuda_stream), "lbdrn_tiff_decode")
+        st = status.cpu().numpy()      # the one host sync; offsets and counts have been copied by now
+    bad = np.flatnonzero(st)
+    if bad.size:
+        i = int(bad[0])
+        raise TiffError(f"segment {i} is damaged: {STATUS_TEXT.get(int(st[i]), st[i])}" +
+                        (f" ({bad.size} damaged segments in all)" if bad.size > 1 else ""), int(st[i]))
+    return planes
+
+
+def read_device(path, device=None):
+    """contiguous [C,H,W] tensor in HBM: int16 storage for 16-bit samples, uint8 for 8-bit ones"""
+    with open(path, "rb") as f:
+        return read_device_bytes(f.read(), path, device)
+
+
+def read_device_bytes(buf, path, device=None):
+    """read_device of a file whose bytes the caller holds already"""
+    import torch
+    scene = parse(buf, path)
+    route = _over_cap(scene.layout, path)
+    dev = _device(device)
+    if route == "host":
+        a = _read_host_deflate(buf, scene)
+        t = torch.from_numpy(a.view(np.int16) if a.dtype.itemsize == 2 else a)
+        return t.to(dev)
+    return decode_device(buf, scene, dev)
+
+
+def read(path, device=None):
+    """numpy uint8 / uint16 [C,H,W], [H,W] for one band: what raster_io._read_tiff returns for the files it reads itself"""
+    with open(path, "rb") as f:
+        buf = f.read()
+    scene = parse(buf, path)
+    if _over_cap(scene.layout, path) == "host":
+        a = _read_host_deflate(buf, scene)
+    else:
+        t = decode_device(buf, scene, _device(device)).cpu().numpy()
+        a = t.view(np.uint16) if t.dtype == np.int16 else t
+    return a[0] if a.shape[0] == 1 else a
