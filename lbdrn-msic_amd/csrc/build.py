@@ -1,4 +1,4 @@
-"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so and liblbdrn_tiff.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so and liblbdrn_tiffw.so for gfx950 with hipcc (in-tree, next to the Python host code).
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -114,6 +114,30 @@ def build_tiff(force=False):
     return TIFF_OUT
 
 
+TIFFW_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_tiffw.so")
+TIFFW_SRCS = ["tiffw.hip"]
+TIFFW_DEPS = ["tiffw.inc", "tiff.inc", "common.hpp", "exports_tiffw.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_tiff.h",
+              "../../include/lbdrn_tiff_write.h"]
+
+
+def build_tiffw(force=False):
+    """liblbdrn_tiffw.so (include/lbdrn_tiff_write.h): the TIFF writer's gather, Deflate encoder and packing, a library of
+    its own like liblbdrn_tiff.so -- same compiler, same flags, its own object file and version script."""
+    if not force and os.path.exists(TIFFW_OUT):
+        t = os.path.getmtime(TIFFW_OUT)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in TIFFW_SRCS + TIFFW_DEPS + ["build.py"]):
+            return TIFFW_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = []
+    for src in TIFFW_SRCS:
+        obj = os.path.join(HERE, src.replace(".hip", ".o"))
+        objs.append(obj)
+        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
+                           "-Wl,--version-script=" + os.path.join(HERE, "exports_tiffw.map"), "-o", TIFFW_OUT] + objs)
+    return TIFFW_OUT
+
+
 def stale():
     if not os.path.exists(OUT):
         return True
@@ -127,6 +151,7 @@ def build(force=False, extra=(), out=None):
         build_jp2k_dec(force)
         build_resid(force)
         build_tiff(force)
+        build_tiffw(force)
     if out == OUT and not force and not stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -160,4 +185,5 @@ if __name__ == "__main__":
         print(JP2K_DEC_OUT)
         print(RESID_OUT)
         print(TIFF_OUT)
+        print(TIFFW_OUT)
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

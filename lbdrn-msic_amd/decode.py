@@ -11,7 +11,11 @@ touch are skipped by the byte sizes in the header, touched ones are decoded on a
 
 A file written with `encode.py --max-error T` carries a residual layer behind its payloads: it is applied by default (to a
 window through the layer's rectangle argument: only the blocks the window touches are decoded); `--no-enhancement` gives the
-base reconstruction."""
+base reconstruction.
+
+`--out-compress deflate [--out-tile N]` writes the raster as a tiled, Deflate-compressed, predictor-2 TIFF
+(raster_io.write_raster_device): at `-sr 1` and for a `--window` the reconstruction is compressed where it lies, in HBM, and only
+the compressed bytes are downloaded; merged tiles and gathered ranks are uploaded once.  Without the flag nothing changes."""
 import argparse
 import os
 import random
@@ -35,9 +39,11 @@ def read_image_header(bitstream):
     return container.unpack_header(bitstream)
 
 
-def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=None):
+def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=None, out=None):
     """Decode one image or tile from the front of `bitstream`; returns the remaining bytes
-    (ref decode.py:56-141).  layer: the tile's residual body (LBR1), applied to the reconstruction in HBM."""
+    (ref decode.py:56-141).  layer: the tile's residual body (LBR1), applied to the reconstruction in HBM.  out: the
+    options of --out-compress (raster_io.write_raster_device); the raster is then written from the reconstruction where it
+    lies, without a host copy of it."""
     nn_payload, bitstream = bitstream[:nn_bytes], bitstream[nn_bytes:]
     base_payload, bitstream = bitstream[:base_bytes], bitstream[base_bytes:]
     base = container.decode_base(base_payload, device=DEVICE, keep_on_device=True)   # ref decode.py:69-73
@@ -48,17 +54,41 @@ def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=N
     # anything is sized by it (ref decode.py:114-120 slices the vector by state_dict shapes)
     need = ops.param_count(ops.make_net(cfg.feature_dim(int(base.shape[0]), D), bc, int(base.shape[0]), nl))
     params = container.decode_weights(nn_payload, expected=need)
+    recon_path = f"{dirname}/{filename}_recon.tif"
+    if write and out is not None:
+        rec = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE, keep_on_device=True)
+        if layer is not None:
+            rec = codec.residual_apply(layer, rec.contiguous())
+        raster_io.write_raster_device(recon_path, rec.contiguous(), **out)
+        test.last_image = None
+        logger.log.info(f"Recon: {recon_path}")
+        return bitstream
     if layer is None:
         image = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE)
     else:
         rec = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE, keep_on_device=True)
         image = ops.from_device_u16(codec.residual_apply(layer, rec.contiguous()))
-    recon_path = f"{dirname}/{filename}_recon.tif"
     test.last_image = image
     if write:
         write_tiff_with_gdal(recon_path, image)
         logger.log.info(f"Recon: {recon_path}")
     return bitstream
+
+
+def out_options(args):
+    """the raster_io.write_raster_device options --out-compress / --out-tile ask for; None: today's writer"""
+    if args.out_compress is None:
+        return None
+    return {"compress": args.out_compress, "tile": args.out_tile}
+
+
+def write_merged(path, image, out):
+    """a host array (merged tiles, gathered ranks) to its raster: uploaded once where --out-compress is given"""
+    if out is None:
+        write_tiff_with_gdal(path, image)
+    else:
+        raster_io.write_raster_device(path, ops.to_device_u16(image, DEVICE) if image.dtype == np.uint16 else
+                                      torch.from_numpy(np.ascontiguousarray(image)).to(DEVICE), **out)
 
 
 def decode_window_main(args, rank, world):
@@ -84,16 +114,30 @@ def decode_window_main(args, rank, world):
     # decode_window_pieces applies a layer by default; only --no-enhancement has anything to say to it
     more = {"enhance": False} if args.no_enhancement else {}
     _, parts = codec.decode_window_pieces(bitstream, args.window, device=DEVICE, take=lambda k, piece: k % world == rank, **more)
-    parts = [(pc.ox, pc.oy, ops.from_device_u16(rec)) for pc, rec in parts]
-    gathered = shard.gather_to_root(parts) if world > 1 else [parts]
-    if rank == 0:
+    out = out_options(args)
+    recon_path = args.out_path or f"{dirname}/{basename[:-4]}_recon_x{x0}_y{y0}_w{w}_h{h}.tif"
+    on_device = out is not None and world == 1      # the pieces stay in HBM, are put together there and written from there
+    if on_device:
         image = None
-        for ox, oy, rec in (rec for part in gathered for rec in part):
+        for pc, rec in parts:
             if image is None:
-                image = np.zeros((rec.shape[0], h, w), rec.dtype)
-            image[:, oy:oy + rec.shape[1], ox:ox + rec.shape[2]] = rec
-        recon_path = args.out_path or f"{dirname}/{basename[:-4]}_recon_x{x0}_y{y0}_w{w}_h{h}.tif"
-        write_tiff_with_gdal(recon_path, image)
+                image = torch.zeros((rec.shape[0], h, w), dtype=rec.dtype, device=rec.device)
+            image[:, pc.oy:pc.oy + rec.shape[1], pc.ox:pc.ox + rec.shape[2]] = rec
+        raster_io.write_raster_device(recon_path, image, **out)
+        gathered = []
+        if args.org_path is not None:
+            image = ops.from_device_u16(image)
+    else:
+        parts = [(pc.ox, pc.oy, ops.from_device_u16(rec)) for pc, rec in parts]
+        gathered = shard.gather_to_root(parts) if world > 1 else [parts]
+    if rank == 0:
+        if not on_device:
+            image = None
+            for ox, oy, rec in (rec for part in gathered for rec in part):
+                if image is None:
+                    image = np.zeros((rec.shape[0], h, w), rec.dtype)
+                image[:, oy:oy + rec.shape[1], ox:ox + rec.shape[2]] = rec
+            write_merged(recon_path, image, out)
         logger.log.info(f"Recon: {recon_path}")
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
         if args.org_path is not None:
@@ -121,7 +165,15 @@ def main(argv=None, shard_tiles=None):
                    help="with --window: where the raster goes (default <name>_recon_x{X0}_y{Y0}_w{W}_h{H}.tif)")
     p.add_argument("--no-enhancement", dest="no_enhancement", action="store_true",
                    help="ignore the residual layer of a file that has one: the base reconstruction")
+    p.add_argument("--out-compress", dest="out_compress", choices=["deflate"], default=None,
+                   help="write the reconstruction as a tiled, Deflate-compressed TIFF (predictor 2), compressed on the GPU")
+    p.add_argument("--out-tile", dest="out_tile", type=int, default=None, metavar="N",
+                   help="with --out-compress: N x N tiles (a multiple of 16; default 256)")
     args = p.parse_args(argv)
+    if args.out_tile is not None and args.out_compress is None:
+        p.error("--out-tile goes with --out-compress")
+    if args.out_tile is not None and (args.out_tile < 16 or args.out_tile % 16):
+        p.error(f"--out-tile {args.out_tile}: a tile side is a positive multiple of 16")
     if args.out_path is not None and args.window is None:
         p.error("-o names the raster of a --window decode")
     rank, world = 0, 1
@@ -183,9 +235,9 @@ def main(argv=None, shard_tiles=None):
                 if merged is None:
                     merged = np.zeros((tiles[t].shape[0], height, width), tiles[t].dtype)
                 merged[:, y0:y0 + h, x0:x0 + w] = tiles[t]
-            write_tiff_with_gdal(recon_path, merged)
+            write_merged(recon_path, merged, out_options(args))
     elif rank == 0:
-        test(bitstream, dirname, filename, nn_list[0], base_list[0], layer=bodies[0])
+        test(bitstream, dirname, filename, nn_list[0], base_list[0], layer=bodies[0], out=out_options(args))
     if rank == 0:
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
         if args.org_path is not None:

@@ -5,7 +5,8 @@ itself produces and consumes: baseline TIFF, uncompressed strips, unsigned 8/16-
 samples, any band count, chunky or planar, either byte order -- and .npy arrays.  Every other TIFF
 -- BigTIFF, tiles, LZW / Deflate / PackBits, predictor 2 -- goes to lbdrn_hip.tiff, which parses it on
 the host and decompresses its segments on the GPU.  Arrays are [C,H,W] (or [H,W] for one band), as
-gdal's ReadAsArray() returns them.
+gdal's ReadAsArray() returns them.  write_raster with a compression or tiling option, and write_raster_device,
+go to lbdrn_hip.tiff_write, which builds and Deflate-compresses the segments on the GPU.
 """
 import struct
 
@@ -55,10 +56,31 @@ def read_raster_device(path, device="cuda:0"):
     return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)
 
 
-def write_raster(path, array):
-    """array [C,H,W]: uint8 / uint16 / float32 / float64 (ref write_tiff_with_gdal)."""
+def _wants_writer(path, compress, tile, rows_per_strip, planar, predictor):
+    """whether the options of a write ask for lbdrn_hip.tiff_write (anything but today's uncompressed planar strips)"""
+    if compress is None and tile is None and rows_per_strip is None and planar == 2 and predictor is None:
+        return False
+    if path.endswith(".npy"):
+        raise ValueError("compress, tile, rows_per_strip, planar and predictor are options of a TIFF, not of a .npy array")
+    if compress not in (None, "none", "deflate"):
+        raise ValueError(f"compress = {compress!r}: None, 'none' and 'deflate' are written")
+    return True
+
+
+def write_raster(path, array, compress=None, tile=None, rows_per_strip=None, planar=2, predictor=None):
+    """array [C,H,W]: uint8 / uint16 / float32 / float64 (ref write_tiff_with_gdal).  With every option at its default the
+    file is what it always was: one uncompressed strip per band.  compress="deflate" (defaults: 256 x 256 tiles, planar,
+    predictor 2), or compress=None with tile= or rows_per_strip=, writes through lbdrn_hip.tiff_write: the array is uploaded
+    and its segments are built and compressed on the GPU.  Integer rasters only."""
     if array.dtype.type not in (np.uint8, np.uint16, np.float32, np.float64):
         raise ValueError("Unsupported data type in this function")
+    if _wants_writer(path, compress, tile, rows_per_strip, planar, predictor):
+        if array.dtype.kind == "f":
+            raise ValueError(f"{array.dtype} rasters are written uncompressed only: compress, tile, rows_per_strip, planar and "
+                             "predictor are for uint8 / uint16 (the reader reads no compressed float raster either)")
+        from . import tiff_write
+        tiff_write.write(path, array, compress or "none", tile, rows_per_strip, planar, predictor)
+        return
     if path.endswith(".npy"):
         np.save(path, array)
         return
@@ -72,6 +94,20 @@ def write_raster(path, array):
         ds.FlushCache()
         return
     _write_tiff(path, array)
+
+
+def write_raster_device(path, tensor, compress="deflate", tile=None, rows_per_strip=None, planar=2, predictor=None):
+    """write_raster for a [C,H,W] tensor that sits in HBM (int16 storage for 16-bit samples, uint8 for 8-bit ones): the
+    segments are built and compressed where the planes lie, and only the compressed bytes are downloaded.  A .npy path
+    takes the host copy it cannot avoid."""
+    if path.endswith(".npy"):
+        _wants_writer(path, None if compress in (None, "none") else compress, tile, rows_per_strip, planar, predictor)
+        a = tensor.cpu().numpy()
+        np.save(path, a.view(np.uint16) if a.dtype == np.int16 else a)
+        return
+    _wants_writer(path, compress, tile, rows_per_strip, planar, predictor)
+    from . import tiff_write
+    tiff_write.write_device(path, tensor, compress or "none", tile, rows_per_strip, planar, predictor)
 
 
 def raster_size(path):
