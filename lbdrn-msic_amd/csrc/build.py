@@ -1,4 +1,4 @@
-"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so and liblbdrn_tiffw.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so, liblbdrn_tiffw.so and liblbdrn_quality.so for gfx950 with hipcc (in-tree, next to the Python host code).
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -138,6 +138,29 @@ def build_tiffw(force=False):
     return TIFFW_OUT
 
 
+QUALITY_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_quality.so")
+QUALITY_SRCS = ["quality.hip"]
+QUALITY_DEPS = ["quality.inc", "common.hpp", "exports_quality.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_quality.h"]
+
+
+def build_quality(force=False):
+    """liblbdrn_quality.so (include/lbdrn_quality.h): the comparison of two rasters in HBM -- error statistics, SSIM and SAM --
+    a library of its own like liblbdrn_tiffw.so -- same compiler, same flags, its own object file and version script."""
+    if not force and os.path.exists(QUALITY_OUT):
+        t = os.path.getmtime(QUALITY_OUT)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in QUALITY_SRCS + QUALITY_DEPS + ["build.py"]):
+            return QUALITY_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = []
+    for src in QUALITY_SRCS:
+        obj = os.path.join(HERE, src.replace(".hip", ".o"))
+        objs.append(obj)
+        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
+                           "-Wl,--version-script=" + os.path.join(HERE, "exports_quality.map"), "-o", QUALITY_OUT] + objs)
+    return QUALITY_OUT
+
+
 def stale():
     if not os.path.exists(OUT):
         return True
@@ -152,6 +175,7 @@ def build(force=False, extra=(), out=None):
         build_resid(force)
         build_tiff(force)
         build_tiffw(force)
+        build_quality(force)
     if out == OUT and not force and not stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -186,4 +210,5 @@ if __name__ == "__main__":
         print(RESID_OUT)
         print(TIFF_OUT)
         print(TIFFW_OUT)
+        print(QUALITY_OUT)
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

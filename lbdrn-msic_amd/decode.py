@@ -15,7 +15,11 @@ base reconstruction.
 
 `--out-compress deflate [--out-tile N]` writes the raster as a tiled, Deflate-compressed, predictor-2 TIFF
 (raster_io.write_raster_device): at `-sr 1` and for a `--window` the reconstruction is compressed where it lies, in HBM, and only
-the compressed bytes are downloaded; merged tiles and gathered ranks are uploaded once.  Without the flag nothing changes."""
+the compressed bytes are downloaded; merged tiles and gathered ranks are uploaded once.  Without the flag nothing changes.
+
+`-org ORG --metrics [--metrics-peak P] [--metrics-json FILE]` adds, behind the `PSNR:` / `Max error:` record, one `Quality band c:`
+line per band and one `Quality:` line for the raster (lbdrn_hip.quality.compare: error statistics, SSIM and the spectral angle,
+computed on the GPU).  The other records are what they are without the flag."""
 import argparse
 import os
 import random
@@ -91,6 +95,26 @@ def write_merged(path, image, out):
                                       torch.from_numpy(np.ascontiguousarray(image)).to(DEVICE), **out)
 
 
+def log_comparison(org_img, rec_img, layer, args):
+    """The records of `-org`: `MSE:` and `PSNR:` (peak fixed at 10000, ref decode.py:218), `Max error:` for a file with a
+    residual layer (a file without one logs what it always logged), and with `--metrics` the lines of
+    lbdrn_hip.quality.compare on the same two arrays behind them."""
+    mse_value = np.mean((org_img.astype(np.float32) - rec_img.astype(np.float32)) ** 2)
+    logger.log.info(f"MSE: {mse_value}")
+    psnr = 10 * np.log10(10000 ** 2 / mse_value)
+    logger.log.info(f"PSNR: {psnr}")
+    if layer is not None:
+        logger.log.info(f"Max error: {int(np.abs(org_img.astype(np.int64) - rec_img.astype(np.int64)).max())}")
+    if args.metrics:
+        from lbdrn_hip import quality
+        q = quality.compare(org_img, rec_img, peak=args.metrics_peak if args.metrics_peak is not None else quality.DEFAULT_PEAK)
+        for line in q.to_records():
+            logger.log.info(line)
+        if args.metrics_json is not None:
+            with open(args.metrics_json, "w") as f:
+                f.write(q.to_json())
+
+
 def decode_window_main(args, rank, world):
     """`--window`: one part of the scene, bit-identical to that crop of the whole reconstruction.  Its records go to
     decode_window.txt: decode.txt, the marker of a finished whole decode, is neither read nor written."""
@@ -143,11 +167,7 @@ def decode_window_main(args, rank, world):
         if args.org_path is not None:
             org_img = raster_io.read_raster(args.org_path)
             org_img = org_img.reshape((-1,) + org_img.shape[-2:])[:, y0:y0 + h, x0:x0 + w]
-            mse_value = np.mean((org_img.astype(np.float32) - image.astype(np.float32)) ** 2)
-            logger.log.info(f"MSE: {mse_value}")
-            logger.log.info(f"PSNR: {10 * np.log10(10000 ** 2 / mse_value)}")    # (no bpsp: a property of the whole file)
-            if layer is not None:      # (a file without a layer logs what it always logged)
-                logger.log.info(f"Max error: {int(np.abs(org_img.astype(np.int64) - image.astype(np.int64)).max())}")
+            log_comparison(org_img, image, layer, args)    # (no bpsp: a property of the whole file)
     if world > 1:
         shard.finish()
     return 0
@@ -169,7 +189,19 @@ def main(argv=None, shard_tiles=None):
                    help="write the reconstruction as a tiled, Deflate-compressed TIFF (predictor 2), compressed on the GPU")
     p.add_argument("--out-tile", dest="out_tile", type=int, default=None, metavar="N",
                    help="with --out-compress: N x N tiles (a multiple of 16; default 256)")
+    p.add_argument("--metrics", action="store_true",
+                   help="with -org: per-band error statistics, SSIM and the spectral angle, compared on the GPU (lbdrn_hip.quality)")
+    p.add_argument("--metrics-peak", dest="metrics_peak", type=float, default=None, metavar="P",
+                   help="with --metrics: the peak of its PSNR and SSIM (default 10000)")
+    p.add_argument("--metrics-json", dest="metrics_json", type=str, default=None, metavar="FILE",
+                   help="with --metrics: write every figure, histograms included, to FILE")
     args = p.parse_args(argv)
+    if args.metrics and args.org_path is None:
+        p.error("--metrics compares with the original: it goes with -org")
+    if (args.metrics_peak is not None or args.metrics_json is not None) and not args.metrics:
+        p.error("--metrics-peak and --metrics-json go with --metrics")
+    if args.metrics_peak is not None and not (args.metrics_peak > 0 and np.isfinite(args.metrics_peak)):
+        p.error(f"--metrics-peak {args.metrics_peak}: a positive finite number")
     if args.out_tile is not None and args.out_compress is None:
         p.error("--out-tile goes with --out-compress")
     if args.out_tile is not None and (args.out_tile < 16 or args.out_tile % 16):
@@ -244,12 +276,7 @@ def main(argv=None, shard_tiles=None):
             org_img = raster_io.read_raster(args.org_path)
             rec_img = raster_io.read_raster(recon_path)
             nbytes = os.path.getsize(args.bin_path)
-            mse_value = np.mean((org_img.astype(np.float32) - rec_img.astype(np.float32)) ** 2)
-            logger.log.info(f"MSE: {mse_value}")
-            psnr = 10 * np.log10(10000 ** 2 / mse_value)    # peak fixed at 10000 (ref decode.py:218)
-            logger.log.info(f"PSNR: {psnr}")
-            if layer is not None:      # (a file without a layer logs what it always logged)
-                logger.log.info(f"Max error: {int(np.abs(org_img.astype(np.int64) - rec_img.astype(np.int64)).max())}")
+            log_comparison(org_img, rec_img, layer, args)
             logger.log.info(f"Total size: {nbytes} bytes, bpsp={nbytes * 8 / np.prod(org_img.shape)}")
             os.remove(recon_path)                             # ref decode.py:223-224
     if world > 1:
