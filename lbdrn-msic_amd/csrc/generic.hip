@@ -7,6 +7,22 @@
 //
 // Summation order of every forward dot product: accumulator starts at the bias, k ascending,
 // one fmaf per term -- identical to an f32 MFMA chain and to oracle/lbdrn_oracle.c.
+//
+// The training step and the autograd backward of this file have an order of their own, and it is a contract: every
+// fused training kernel is held to this step, so this step is held to a bit pattern -- oracle/lbdrn_oracle.c:
+// orc_step_ordered restates it in scalar float32, tests/test_gpu_generic_step_bits.py compares bit for bit.
+//   head     dz = ((2 (y - t)) * inv) * (y (1 - y)), inv = 1.0f / ((float)B * (float)C); autograd: dz = dy * (y (1 - y))
+//   loss     float64: thread (block b, lane l) of k_loss_grad<<<64, 256>>> adds (double)(d * d) for e = 256 b + l + 16384 i,
+//            i ascending; the 256-lane tree red[l] += red[l + o], o = 128 .. 1; the 64 partials in index order
+//   GradW    the batch in slices of GRAD_SLICE = 256 rows; within a slice dW[j][k] is the chain
+//            acc = fmaf(dz[b][j], in[b][k], acc) from +0.0f, b ascending, and db[j] the same chain with in = 1.0f; the
+//            slices are then added in float32, acc += part[z] from 0.0f, z ascending
+//   BackDx   v = fmaf(dz[b][j], W[j][k], v) from 0.0f, j ascending; Sine stores (v * cos(30 z)) * 30.0f, ReLU
+//            cos != 0 ? v : 0; InputDx is the same chain stored as it is
+//   Adam     the three lines of k_adam
+// A chain that ends in a part-filled 16-wide k-tile runs on through fmaf(0, 0, acc) (the zero padding of the tile),
+// which turns an accumulator of -0.0f into +0.0f.  -ffp-contract=off and correctly rounded division / sqrt
+// (csrc/build.py) keep every other operation the one that is written.
 #include <stdarg.h>
 
 #include <cmath>

@@ -322,7 +322,8 @@ double orc_eval_sse(const uint16_t *msb, const float *labels, int C, int H, int 
  * single-tensor math (torch/optim/adam.py: lerp_, mul_/addcmul_, addcdiv_) with defaults
  * beta=(0.9,0.999), eps=1e-8 (encode.py:84).  Gradient sums run in float64 and are rounded to
  * float32 once: the reference's sgemm order is unspecified, so this is the tolerance target
- * (1e-5 relative), not a bit pattern.  step is the 1-based Adam step count.
+ * (1e-5 relative) of every training kernel, not a bit pattern.  The bit pattern of the generic step
+ * (csrc/generic.hip) is orc_step_ordered below.  step is the 1-based Adam step count.
  * grads (optional) receives the float32 gradient vector; if apply_adam == 0 only loss/grads. */
 int orc_train_step(float *params, float *m, float *v, int F, int bc, int C, int nl,
                    const float *x, const float *t, int B, double lr, int step, int apply_adam,
@@ -403,5 +404,252 @@ int orc_train_step(float *params, float *m, float *v, int F, int bc, int C, int 
     free(offW);
     free(zs);
     free(g);
+    return 0;
+}
+
+/* ---------------------------------------------------------------- the generic step in its own order */
+
+/* The generic training step and autograd backward of csrc/generic.hip, restated operation by operation in scalar
+ * float32 so that the result is a bit pattern (orc_train_step above stays the float64 tolerance target).  The order,
+ * as generic.hip's comments state it:
+ *   forward    every pre-activation a chain acc = fmaf(x[k], W[j][k], acc) from the bias, k ascending; the tape keeps
+ *              cos(30 z) per hidden unit (ReLU: z > 0 ? 1 : 0)
+ *   head       dz = ((2 (y - t)) * inv) * (y (1 - y)), inv = 1 / ((float)B (float)C); autograd: dz = dy * (y (1 - y))
+ *   loss       float64: thread (block b, lane l) of a <<<64, 256>>> grid adds (double)(d * d) for e = 256 b + l + 16384 i,
+ *              i ascending; the 256-lane tree red[l] += red[l + o], o = 128 .. 1; the 64 partials in index order
+ *   GradW      the batch in slices of `slice` rows (GRAD_SLICE = 256); within a slice dW[j][k] a chain
+ *              acc = fmaf(dz[b][j], in[b][k], acc) from +0, b ascending, db[j] the same chain with in = 1; the slices
+ *              then added in float32, acc += part[z] from 0, z ascending
+ *   BackDx     v = fmaf(dz[b][j], W[j][k], v) from 0, j ascending; Sine stores (v * cos) * 30, ReLU cos != 0 ? v : 0
+ *   InputDx    the same chain, stored as it is
+ *   Adam       k_adam's three lines
+ * A chain that ends in a part-filled 16-wide k-tile of the MFMA GEMM runs on through fmaf(0, 0, acc), which turns an
+ * accumulator of -0 into +0: pad16 restates that, so that the signs of zeros agree too.
+ * `slice` and `flags` exist for tests/test_generic_step_ordered_host.py, which shows that its inputs tell these orders
+ * apart; the kernels' order is slice = 256, flags = 0. */
+#define ORC_REVERSE_SLICES 1 /* add the slices z descending */
+#define ORC_FACTOR_RIGHT 2   /* v * (cos * 30) instead of (v * cos) * 30 */
+#define ORC_DROP_LAST_ROW 4  /* the last slice loses the last row of the batch */
+
+/* range bookkeeping: the smallest nonzero magnitude and the number of non-finite values among every product,
+ * accumulator and stored value of one call (products taken exactly, in float64) */
+static int g_seen_on = 0;
+static double g_seen_min = 0.0;
+static int64_t g_seen_bad = 0;
+
+static inline void seen(double v)
+{
+    double a = fabs(v);
+    if (!(a <= 1.7976931348623157e308)) ++g_seen_bad; /* Inf or NaN */
+    else if (a != 0.0 && a < g_seen_min) g_seen_min = a;
+}
+
+static inline float chain(float a, float b, float acc)
+{
+    float r = fmaf(a, b, acc);
+    if (g_seen_on) {
+        seen((double)a * (double)b);
+        seen(r);
+    }
+    return r;
+}
+
+static inline float keep(float v)
+{
+    if (g_seen_on) seen(v);
+    return v;
+}
+
+/* a chain of n terms on 16-wide k-tiles: the zero padding of a part-filled last tile */
+static inline float pad16(float acc, int64_t n) { return (n & 15) ? fmaf(0.0f, 0.0f, acc) : acc; }
+
+static void linear_ordered(const float *Wt, const float *b, int nout, int nin, const float *x, float *z)
+{
+    for (int j = 0; j < nout; ++j) {
+        float acc = b[j];
+        const float *w = Wt + (int64_t)j * nin;
+        for (int k = 0; k < nin; ++k) acc = chain(x[k], w[k], acc);
+        z[j] = keep(pad16(acc, nin));
+    }
+}
+
+/* gW[M][nin] and, behind it, gb[M] of one nn.Linear from dz [B][M] and its input in [B][nin] */
+static void grad_ordered(const float *dz, const float *in, int B, int M, int nin, int slice, int flags,
+                         float *part, float *tot, float *gW)
+{
+    const int N = nin + 1;
+    const int64_t MN = (int64_t)M * N;
+    const int nsl = (B + slice - 1) / slice;
+    for (int64_t e = 0; e < MN; ++e) tot[e] = 0.0f;
+    for (int zi = 0; zi < nsl; ++zi) {
+        const int z = (flags & ORC_REVERSE_SLICES) ? nsl - 1 - zi : zi;
+        const int b0 = z * slice;
+        int b1 = b0 + slice < B ? b0 + slice : B;
+        if ((flags & ORC_DROP_LAST_ROW) && z == nsl - 1) --b1;
+        for (int64_t e = 0; e < MN; ++e) part[e] = 0.0f;
+        for (int b = b0; b < b1; ++b) {
+            const float *row_in = in + (int64_t)b * nin;
+            for (int j = 0; j < M; ++j) {
+                const float d = dz[(int64_t)b * M + j];
+                float *p = part + (int64_t)j * N;
+                for (int k = 0; k < nin; ++k) p[k] = chain(d, row_in[k], p[k]);
+                p[nin] = chain(d, 1.0f, p[nin]);
+            }
+        }
+        for (int64_t e = 0; e < MN; ++e) tot[e] = keep(tot[e] + keep(pad16(part[e], b1 - b0)));
+    }
+    for (int j = 0; j < M; ++j) {
+        for (int k = 0; k < nin; ++k) gW[(int64_t)j * nin + k] = tot[(int64_t)j * N + k];
+        gW[(int64_t)M * nin + j] = tot[(int64_t)j * N + nin];
+    }
+}
+
+/* out[b][k] = sum_j dz[b][j] W[j][k], j ascending from 0: the chain of BackDx and InputDx */
+static inline float back_chain(const float *dzrow, const float *W, int nup, int ncols, int k)
+{
+    float v = 0.0f;
+    for (int j = 0; j < nup; ++j) v = chain(dzrow[j], W[(int64_t)j * ncols + k], v);
+    return keep(pad16(v, nup));
+}
+
+/* One generic step (dy == NULL: lbdrn_train_step on targets t) or one generic backward from an upstream gradient
+ * (dy != NULL: lbdrn_forward_tape + lbdrn_backward; t, the loss and Adam take no part).  params / m / v are updated in
+ * place where apply_adam; loss_out, grads [param_count], y_out [B][C], dx_out [B][F] and range [2] (smallest nonzero
+ * magnitude seen, number of non-finite values) are optional. */
+int orc_step_ordered(float *params, float *m, float *v, int F, int bc, int C, int nl, const float *x,
+                     const float *t, const float *dy, int B, double lr, int64_t step, int apply_adam, int slice,
+                     int flags, float *loss_out, float *grads, float *y_out, float *dx_out, double *range)
+{
+    if (nl < 1 || B < 1 || slice < 1 || (!dy && !t)) return -1;
+    if (!dy && apply_adam && (!m || !v || step < 1)) return -1;
+    g_seen_on = range != 0;
+    g_seen_min = 1.7976931348623157e308;
+    g_seen_bad = 0;
+    const int relu = g_hidden_relu;
+    const int64_t NP = param_count(F, bc, C, nl);
+    const int64_t act = (int64_t)B * bc, total = (int64_t)B * C;
+    const int rows = bc > C ? bc : C, cols = (bc > F ? bc : F) + 1;
+    float *h = (float *)malloc(sizeof(float) * (2 * nl * act + 2 * total + 2 * act + NP + 2 * (int64_t)rows * cols + bc));
+    float *cs = h + nl * act, *y = cs + nl * act, *dzl = y + total;
+    float *dzp[2] = {dzl + total, dzl + total + act};
+    float *g = dzp[1] + act, *part = g + NP, *tot = part + (int64_t)rows * cols, *zrow = tot + (int64_t)rows * cols;
+    int64_t *off = (int64_t *)malloc(sizeof(int64_t) * (nl + 1));
+    int64_t o = 0;
+    for (int l = 0; l < nl; ++l) { off[l] = o; o += (int64_t)bc * (l ? bc : F) + bc; }
+    off[nl] = o;
+
+    /* forward with tape */
+    for (int l = 0; l < nl; ++l) {
+        const int nin = l ? bc : F;
+        const float *in = l ? h + (l - 1) * act : x;
+        const float *W = params + off[l];
+        for (int b = 0; b < B; ++b) {
+            linear_ordered(W, W + (int64_t)bc * nin, bc, nin, in + (int64_t)b * nin, zrow);
+            float *hb = h + l * act + (int64_t)b * bc, *cb = cs + l * act + (int64_t)b * bc;
+            for (int j = 0; j < bc; ++j) {
+                const float z = zrow[j];
+                if (relu) {
+                    hb[j] = z > 0.0f ? z : 0.0f;
+                    cb[j] = z > 0.0f ? 1.0f : 0.0f;
+                } else {
+                    const float a = keep(30.0f * z);
+                    hb[j] = keep(canon_sincos(a, 0));
+                    cb[j] = keep(canon_sincos(a, 1));
+                }
+            }
+        }
+    }
+    {
+        const float *W = params + off[nl];
+        float *zc = (float *)malloc(sizeof(float) * C);
+        for (int b = 0; b < B; ++b) {
+            linear_ordered(W, W + (int64_t)C * bc, C, bc, h + (nl - 1) * act + (int64_t)b * bc, zc);
+            for (int c = 0; c < C; ++c) y[(int64_t)b * C + c] = keep(canon_sigmoid(zc[c]));
+        }
+        free(zc);
+    }
+    if (y_out) memcpy(y_out, y, sizeof(float) * total);
+
+    /* head */
+    if (dy) {
+        for (int64_t e = 0; e < total; ++e) dzl[e] = keep(dy[e] * keep(y[e] * keep(1.0f - y[e])));
+    } else {
+        const float inv = 1.0f / ((float)B * (float)C);
+        for (int64_t e = 0; e < total; ++e) {
+            const float d = keep(y[e] - t[e]);
+            const float dyv = keep(keep(2.0f * d) * inv);
+            dzl[e] = keep(dyv * keep(y[e] * keep(1.0f - y[e])));
+        }
+        /* loss: k_loss_grad<<<64, 256>>> + k_finish_loss */
+        double partial[64], red[256], s = 0.0;
+        for (int blk = 0; blk < 64; ++blk) {
+            for (int ln = 0; ln < 256; ++ln) {
+                double acc = 0.0;
+                for (int64_t e = (int64_t)blk * 256 + ln; e < total; e += 64 * 256) {
+                    const float d = y[e] - t[e];
+                    acc += (double)keep(d * d);
+                }
+                red[ln] = acc;
+            }
+            for (int w = 128; w > 0; w >>= 1)
+                for (int ln = 0; ln < w; ++ln) red[ln] += red[ln + w];
+            partial[blk] = red[0];
+        }
+        for (int i = 0; i < 64; ++i) s += partial[i];
+        if (loss_out) *loss_out = keep((float)(s / (double)total));
+    }
+
+    /* backward */
+    grad_ordered(dzl, h + (nl - 1) * act, B, C, bc, slice, flags, part, tot, g + off[nl]);
+    const float *dz_up = dzl, *W_up = params + off[nl];
+    int n_up = C;
+    for (int l = nl - 1; l >= 0; --l) {
+        float *d = dzp[l & 1];
+        const float *cl = cs + l * act;
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < bc; ++k) {
+                const float vv = back_chain(dz_up + (int64_t)b * n_up, W_up, n_up, bc, k);
+                const float c = cl[(int64_t)b * bc + k];
+                float r;
+                if (relu) r = c != 0.0f ? vv : 0.0f;
+                else if (flags & ORC_FACTOR_RIGHT) r = vv * keep(c * 30.0f);
+                else r = keep(vv * c) * 30.0f;
+                d[(int64_t)b * bc + k] = keep(r);
+            }
+        const int nin = l ? bc : F;
+        grad_ordered(d, l ? h + (l - 1) * act : x, B, bc, nin, slice, flags, part, tot, g + off[l]);
+        dz_up = d;
+        n_up = bc;
+        W_up = params + off[l];
+    }
+    if (dx_out)
+        for (int b = 0; b < B; ++b)
+            for (int k = 0; k < F; ++k) dx_out[(int64_t)b * F + k] = back_chain(dz_up + (int64_t)b * bc, params, bc, F, k);
+    if (grads) memcpy(grads, g, sizeof(float) * NP);
+
+    /* Adam: k_adam / launch_adam */
+    if (!dy && apply_adam) {
+        const float b2 = 0.999f, eps = 1e-8f;
+        const float w1 = (float)(1.0 - 0.9), w2 = (float)(1.0 - 0.999);
+        const double bc1 = 1.0 - pow(0.9, (double)step), bc2 = 1.0 - pow(0.999, (double)step);
+        const float step_size = (float)(lr / bc1);
+        const float bc2s = (float)sqrt(bc2);
+        for (int64_t i = 0; i < NP; ++i) {
+            const float gi = g[i];
+            const float mi = keep(m[i] + keep(w1 * keep(gi - m[i])));
+            const float vi = keep(keep(v[i] * b2) + keep(w2 * keep(gi * gi)));
+            const float denom = keep(keep(sqrtf(vi)) / bc2s) + eps;
+            m[i] = mi;
+            v[i] = vi;
+            params[i] = keep(params[i] + keep((-step_size) * keep(mi / denom)));
+        }
+    }
+    if (range) {
+        range[0] = g_seen_min;
+        range[1] = (double)g_seen_bad;
+    }
+    g_seen_on = 0;
+    free(off);
+    free(h);
     return 0;
 }

@@ -207,6 +207,71 @@ def train_step(params, m, v, F, bc, C, nl, x, t, lr, step, apply_adam=True):
     return loss.value, grads
 
 
+GRAD_SLICE = 256        # batch rows per GradW slice (csrc/generic.hip)
+REVERSE_SLICES, FACTOR_RIGHT, DROP_LAST_ROW = 1, 2, 4   # orc_step_ordered's flags: orders the kernels do NOT use
+
+
+def _step_ordered(params, m, v, F, bc, C, nl, x, t, dy, lr, step, apply_adam, slice_rows, flags, want_dx, want_range):
+    x = _c(x, np.float32)
+    B = x.shape[0]
+    assert params.dtype == np.float32 and params.flags.c_contiguous and params.size == param_count(F, bc, C, nl)
+    assert x.shape == (B, F)
+    t = None if t is None else _c(t, np.float32)
+    dy = None if dy is None else _c(dy, np.float32)
+    for a in (t, dy):
+        assert a is None or a.shape == (B, C)
+    grads = np.empty_like(params)
+    y = np.empty((B, C), np.float32)
+    dx = np.empty((B, F), np.float32) if want_dx else None
+    rng = np.zeros(2, np.float64) if want_range else None
+    loss = ctypes.c_float(0)
+    rc = lib().orc_step_ordered(_p(params), _p(m), _p(v), F, bc, C, nl, _p(x), _p(t), _p(dy), B, ctypes.c_double(lr),
+                                ctypes.c_int64(int(step)), int(apply_adam), int(slice_rows), int(flags),
+                                ctypes.byref(loss), _p(grads), _p(y), _p(dx), _p(rng))
+    assert rc == 0, rc
+    return np.float32(loss.value), grads, y, dx, rng
+
+
+def train_step_ordered(params, m, v, F, bc, C, nl, x, t, lr, step, apply_adam=True, slice_rows=GRAD_SLICE, flags=0,
+                       want_range=False):
+    """The generic training step (lbdrn_train_step, csrc/generic.hip) in its own order, bit for bit: every sum a float32
+    fmaf chain in the kernels' order, where train_step() sums in float64.  params / m / v (float32 arrays) are updated in
+    place where apply_adam.  Returns (loss float32, grads, params, m, v) -- the same three arrays, after the update --
+    and, with want_range, a sixth item: (smallest nonzero magnitude among every product, accumulator and stored value,
+    number of non-finite ones).  slice_rows and flags select another order than the kernels' (for the host test that
+    shows its inputs can tell)."""
+    for a in (m, v):
+        assert a.dtype == np.float32 and a.flags.c_contiguous and a.size == params.size
+    loss, grads, _, _, rng = _step_ordered(params, m, v, F, bc, C, nl, x, t, None, lr, step, apply_adam, slice_rows,
+                                           flags, False, want_range)
+    out = (loss, grads, params, m, v)
+    return out + ((float(rng[0]), int(rng[1])),) if want_range else out
+
+
+def backward_ordered(params, F, bc, C, nl, x, dy, want_dx=True):
+    """lbdrn_forward_tape + lbdrn_backward in their own order, bit for bit: -> (y [B,C], grads, dL/dx [B,F] or None)
+    for an upstream gradient dy [B,C]."""
+    _, grads, y, dx, _ = _step_ordered(params, None, None, F, bc, C, nl, x, None, dy, 0.0, 0, False, GRAD_SLICE, 0,
+                                       want_dx, False)
+    return y, grads, dx
+
+
+def train_epoch_ordered(img, K, D, cfg, params, m, v, bc, nl, perm, bs, lr, step0):
+    """generic_train_epoch in its own order: the rows and labels of perm's pixels (features / split_bits, bit-exact
+    against the device), minibatches of bs rows with a short last one, Adam steps step0 + 1 ..  params / m / v are
+    updated in place.  Returns the float32 losses, one per minibatch."""
+    msb, lab, mx = split_bits(img, K)
+    feats = features(msb, D, cfg, mx)
+    C = msb.shape[0]
+    F = feats.shape[1]
+    perm = np.asarray(perm, np.int64)
+    losses = []
+    for s, first in enumerate(range(0, perm.size, bs)):
+        b = perm[first:first + bs]
+        losses.append(train_step_ordered(params, m, v, F, bc, C, nl, feats[b], lab[b], lr, step0 + s + 1)[0])
+    return np.array(losses, np.float32)
+
+
 def lr_schedule(lr, epochs):
     """StepLR(step_size=max(1,int(e/3)), gamma=0.1) stepped once per epoch (encode.py:85,98):
     learning rate in force during epoch e (0-based), chained float64 multiplies."""
