@@ -1,4 +1,4 @@
-"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so, liblbdrn_tiffw.so and liblbdrn_quality.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so, liblbdrn_tiffw.so, liblbdrn_quality.so and liblbdrn_pyramid.so for gfx950 with hipcc (in-tree, next to the Python host code).
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -161,6 +161,29 @@ def build_quality(force=False):
     return QUALITY_OUT
 
 
+PYRAMID_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_pyramid.so")
+PYRAMID_SRCS = ["pyramid.hip"]
+PYRAMID_DEPS = ["pyramid.inc", "common.hpp", "exports_pyramid.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_pyramid.h"]
+
+
+def build_pyramid(force=False):
+    """liblbdrn_pyramid.so (include/lbdrn_pyramid.h): the overview levels of a raster in HBM, a library of its own like
+    liblbdrn_quality.so -- same compiler, same flags, its own object file and version script."""
+    if not force and os.path.exists(PYRAMID_OUT):
+        t = os.path.getmtime(PYRAMID_OUT)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in PYRAMID_SRCS + PYRAMID_DEPS + ["build.py"]):
+            return PYRAMID_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = []
+    for src in PYRAMID_SRCS:
+        obj = os.path.join(HERE, src.replace(".hip", ".o"))
+        objs.append(obj)
+        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
+                           "-Wl,--version-script=" + os.path.join(HERE, "exports_pyramid.map"), "-o", PYRAMID_OUT] + objs)
+    return PYRAMID_OUT
+
+
 def stale():
     if not os.path.exists(OUT):
         return True
@@ -176,6 +199,7 @@ def build(force=False, extra=(), out=None):
         build_tiff(force)
         build_tiffw(force)
         build_quality(force)
+        build_pyramid(force)
     if out == OUT and not force and not stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -211,4 +235,5 @@ if __name__ == "__main__":
         print(TIFF_OUT)
         print(TIFFW_OUT)
         print(QUALITY_OUT)
+        print(PYRAMID_OUT)
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

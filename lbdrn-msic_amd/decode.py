@@ -16,6 +16,9 @@ base reconstruction.
 `--out-compress deflate [--out-tile N]` writes the raster as a tiled, Deflate-compressed, predictor-2 TIFF
 (raster_io.write_raster_device): at `-sr 1` and for a `--window` the reconstruction is compressed where it lies, in HBM, and only
 the compressed bytes are downloaded; merged tiles and gathered ranks are uploaded once.  Without the flag nothing changes.
+With it, `--out-overviews auto|N [--out-resampling average|nearest] [--out-nodata V]` adds overview levels, reduced on the GPU
+from the reconstruction where it lies (lbdrn_hip.pyramid), and `--out-georef FILE` copies FILE's georeferencing tags onto the
+output.  No log record changes.
 
 `-org ORG --metrics [--metrics-peak P] [--metrics-json FILE]` adds, behind the `PSNR:` / `Max error:` record, one `Quality band c:`
 line per band and one `Quality:` line for the raster (lbdrn_hip.quality.compare: error statistics, SSIM and the spectral angle,
@@ -80,10 +83,16 @@ def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=N
 
 
 def out_options(args):
-    """the raster_io.write_raster_device options --out-compress / --out-tile ask for; None: today's writer"""
+    """the raster_io.write_raster_device options --out-compress / --out-tile / --out-overviews / --out-resampling / --out-nodata /
+    --out-georef ask for; None: today's writer"""
     if args.out_compress is None:
         return None
-    return {"compress": args.out_compress, "tile": args.out_tile}
+    out = {"compress": args.out_compress, "tile": args.out_tile}
+    if args.out_overviews is not None:
+        out.update(overviews=args.out_overviews, resampling=args.out_resampling or "average", nodata=args.out_nodata)
+    if args.out_georef is not None:
+        out["geo"] = raster_io.read_geo_tags(args.out_georef) or None
+    return out
 
 
 def write_merged(path, image, out):
@@ -189,6 +198,15 @@ def main(argv=None, shard_tiles=None):
                    help="write the reconstruction as a tiled, Deflate-compressed TIFF (predictor 2), compressed on the GPU")
     p.add_argument("--out-tile", dest="out_tile", type=int, default=None, metavar="N",
                    help="with --out-compress: N x N tiles (a multiple of 16; default 256)")
+    p.add_argument("--out-overviews", dest="out_overviews", type=str, default=None, metavar="auto|N",
+                   help="with --out-compress: add overview levels, reduced on the GPU (auto: until a level fits one tile)")
+    p.add_argument("--out-resampling", dest="out_resampling", choices=["average", "nearest"], default=None,
+                   help="with --out-overviews: how a level is reduced from the one before it (default average)")
+    p.add_argument("--out-nodata", dest="out_nodata", type=int, default=None, metavar="V",
+                   help="with --out-overviews: samples of this value do not enter an average")
+    p.add_argument("--out-georef", dest="out_georef", type=str, default=None, metavar="FILE",
+                   help="with --out-compress: copy FILE's georeferencing tags onto the output (the original scene, or any raster "
+                        "on the same grid)")
     p.add_argument("--metrics", action="store_true",
                    help="with -org: per-band error statistics, SSIM and the spectral angle, compared on the GPU (lbdrn_hip.quality)")
     p.add_argument("--metrics-peak", dest="metrics_peak", type=float, default=None, metavar="P",
@@ -206,6 +224,22 @@ def main(argv=None, shard_tiles=None):
         p.error("--out-tile goes with --out-compress")
     if args.out_tile is not None and (args.out_tile < 16 or args.out_tile % 16):
         p.error(f"--out-tile {args.out_tile}: a tile side is a positive multiple of 16")
+    for flag, value in (("--out-overviews", args.out_overviews), ("--out-resampling", args.out_resampling),
+                        ("--out-nodata", args.out_nodata), ("--out-georef", args.out_georef)):
+        if value is not None and args.out_compress is None:
+            p.error(f"{flag} goes with --out-compress")
+    if (args.out_resampling is not None or args.out_nodata is not None) and args.out_overviews is None:
+        p.error("--out-resampling and --out-nodata go with --out-overviews")
+    if args.out_overviews is not None:
+        from lbdrn_hip import pyramid
+        try:
+            args.out_overviews = pyramid.parse_overviews(args.out_overviews)
+        except ValueError:
+            p.error(f"--out-overviews {args.out_overviews}: auto or a count of levels")
+    if args.out_nodata is not None and not 0 <= args.out_nodata <= 65535:
+        p.error(f"--out-nodata {args.out_nodata}: a sample value")
+    if args.out_georef is not None and not os.path.exists(args.out_georef):
+        p.error(f"--out-georef {args.out_georef}: no such file")
     if args.out_path is not None and args.window is None:
         p.error("-o names the raster of a --window decode")
     rank, world = 0, 1

@@ -6,7 +6,9 @@ samples, any band count, chunky or planar, either byte order -- and .npy arrays.
 -- BigTIFF, tiles, LZW / Deflate / PackBits, predictor 2 -- goes to lbdrn_hip.tiff, which parses it on
 the host and decompresses its segments on the GPU.  Arrays are [C,H,W] (or [H,W] for one band), as
 gdal's ReadAsArray() returns them.  write_raster with a compression or tiling option, and write_raster_device,
-go to lbdrn_hip.tiff_write, which builds and Deflate-compresses the segments on the GPU.
+go to lbdrn_hip.tiff_write, which builds and Deflate-compresses the segments on the GPU -- with overviews= the overview
+levels too, reduced on the GPU by lbdrn_hip.pyramid, and with geo= the georeferencing tags read_geo_tags copied from
+another file.  read_raster(path, overview=k) reads level k of such a file.
 """
 import struct
 
@@ -24,7 +26,31 @@ def _gdal():
         return None
 
 
-def read_raster(path):
+def _overview_ifd(buf, path, overview):
+    """the chain position of overview level `overview` >= 1: the IFDs whose NewSubfileType has bit 0 set, in file order"""
+    from . import tiff
+    levels = tiff.overview_ifds(buf, path)
+    if not 1 <= overview <= len(levels):
+        raise IndexError(f"{path}: overview {overview} of a file that has {len(levels)} overview level{'s' * (len(levels) != 1)}")
+    return levels[overview - 1]
+
+
+def _check_overview(path, overview):
+    if isinstance(overview, bool) or int(overview) != overview or overview < 0:
+        raise ValueError(f"overview = {overview!r}: 0 (the full resolution) or the number of a level")
+    if overview and path.endswith(".npy"):
+        raise IndexError(f"{path}: overview {overview} of a .npy array, which has no overview levels")
+    return int(overview)
+
+
+def read_raster(path, overview=0):
+    """overview=k >= 1: level k of a pyramidal TIFF, through this package's parser and the GPU reader even where GDAL
+    imports; IndexError where the file has fewer levels."""
+    if _check_overview(path, overview):
+        from . import tiff
+        with open(path, "rb") as f:
+            buf = f.read()
+        return tiff.read(path, ifd=_overview_ifd(buf, path, overview))
     if path.endswith(".npy"):
         return np.load(path)
     g = _gdal()
@@ -33,10 +59,16 @@ def read_raster(path):
     return _read_tiff(path)
 
 
-def read_raster_device(path, device="cuda:0"):
+def read_raster_device(path, device="cuda:0", overview=0):
     """The raster as a contiguous [C,H,W] tensor on `device`, for callers that want the planes left in HBM: 16-bit samples as
-    int16 storage, like every plane of this package.  A tiled or compressed TIFF never passes through host arrays."""
+    int16 storage, like every plane of this package.  A tiled or compressed TIFF never passes through host arrays.
+    overview=k >= 1: level k of a pyramidal TIFF, as read_raster has it."""
     import torch
+    if _check_overview(path, overview):
+        from . import tiff
+        with open(path, "rb") as f:
+            buf = f.read()
+        return tiff.read_device_bytes(buf, path, device, ifd=_overview_ifd(buf, path, overview))
     a = None
     if path.endswith(".npy") or _gdal() is not None:
         a = read_raster(path)
@@ -56,30 +88,56 @@ def read_raster_device(path, device="cuda:0"):
     return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)
 
 
-def _wants_writer(path, compress, tile, rows_per_strip, planar, predictor):
+def read_geo_tags(path):
+    """The georeferencing tags of a TIFF's first IFD as [(tag, type, count, little-endian value bytes)] -- what write_raster
+    takes as `geo`; [] for a file without them and for a .npy array."""
+    if path.endswith(".npy"):
+        return []
+    from . import tiff
+    with open(path, "rb") as f:
+        return tiff.read_geo_tags(f.read(), path)
+
+
+def _wants_writer(path, compress, tile, rows_per_strip, planar, predictor, overviews=None, resampling="average", nodata=None, geo=None):
     """whether the options of a write ask for lbdrn_hip.tiff_write (anything but today's uncompressed planar strips)"""
-    if compress is None and tile is None and rows_per_strip is None and planar == 2 and predictor is None:
+    new = overviews is not None or resampling != "average" or nodata is not None or geo is not None
+    if compress is None and tile is None and rows_per_strip is None and planar == 2 and predictor is None and not new:
         return False
     if path.endswith(".npy"):
+        if new:
+            raise ValueError("overviews, resampling, nodata and geo are options of a TIFF, not of a .npy array")
         raise ValueError("compress, tile, rows_per_strip, planar and predictor are options of a TIFF, not of a .npy array")
     if compress not in (None, "none", "deflate"):
         raise ValueError(f"compress = {compress!r}: None, 'none' and 'deflate' are written")
     return True
 
 
-def write_raster(path, array, compress=None, tile=None, rows_per_strip=None, planar=2, predictor=None):
+def _new_options(overviews, resampling, nodata, geo):
+    """the overview and georeferencing options that were given, as keywords: a write without them is the call it always was"""
+    given = {"overviews": overviews, "nodata": nodata, "geo": geo}
+    out = {k: v for k, v in given.items() if v is not None}
+    if resampling != "average":
+        out["resampling"] = resampling
+    return out
+
+
+def write_raster(path, array, compress=None, tile=None, rows_per_strip=None, planar=2, predictor=None, overviews=None,
+                 resampling="average", nodata=None, geo=None):
     """array [C,H,W]: uint8 / uint16 / float32 / float64 (ref write_tiff_with_gdal).  With every option at its default the
     file is what it always was: one uncompressed strip per band.  compress="deflate" (defaults: 256 x 256 tiles, planar,
     predictor 2), or compress=None with tile= or rows_per_strip=, writes through lbdrn_hip.tiff_write: the array is uploaded
-    and its segments are built and compressed on the GPU.  Integer rasters only."""
+    and its segments are built and compressed on the GPU.  Integer rasters only.  overviews="auto" or a count adds that many
+    overview levels, reduced on the GPU (resampling "average" or "nearest", nodata a value that does not enter an average);
+    geo -- what read_geo_tags returns -- is copied onto the full-resolution IFD.  Either goes through the same writer."""
     if array.dtype.type not in (np.uint8, np.uint16, np.float32, np.float64):
         raise ValueError("Unsupported data type in this function")
-    if _wants_writer(path, compress, tile, rows_per_strip, planar, predictor):
+    if _wants_writer(path, compress, tile, rows_per_strip, planar, predictor, overviews, resampling, nodata, geo):
         if array.dtype.kind == "f":
             raise ValueError(f"{array.dtype} rasters are written uncompressed only: compress, tile, rows_per_strip, planar and "
                              "predictor are for uint8 / uint16 (the reader reads no compressed float raster either)")
         from . import tiff_write
-        tiff_write.write(path, array, compress or "none", tile, rows_per_strip, planar, predictor)
+        tiff_write.write(path, array, compress or "none", tile, rows_per_strip, planar, predictor,
+                         **_new_options(overviews, resampling, nodata, geo))
         return
     if path.endswith(".npy"):
         np.save(path, array)
@@ -96,18 +154,21 @@ def write_raster(path, array, compress=None, tile=None, rows_per_strip=None, pla
     _write_tiff(path, array)
 
 
-def write_raster_device(path, tensor, compress="deflate", tile=None, rows_per_strip=None, planar=2, predictor=None):
+def write_raster_device(path, tensor, compress="deflate", tile=None, rows_per_strip=None, planar=2, predictor=None, overviews=None,
+                        resampling="average", nodata=None, geo=None):
     """write_raster for a [C,H,W] tensor that sits in HBM (int16 storage for 16-bit samples, uint8 for 8-bit ones): the
     segments are built and compressed where the planes lie, and only the compressed bytes are downloaded.  A .npy path
     takes the host copy it cannot avoid."""
     if path.endswith(".npy"):
-        _wants_writer(path, None if compress in (None, "none") else compress, tile, rows_per_strip, planar, predictor)
+        _wants_writer(path, None if compress in (None, "none") else compress, tile, rows_per_strip, planar, predictor, overviews,
+                      resampling, nodata, geo)
         a = tensor.cpu().numpy()
         np.save(path, a.view(np.uint16) if a.dtype == np.int16 else a)
         return
-    _wants_writer(path, compress, tile, rows_per_strip, planar, predictor)
+    _wants_writer(path, compress, tile, rows_per_strip, planar, predictor, overviews, resampling, nodata, geo)
     from . import tiff_write
-    tiff_write.write_device(path, tensor, compress or "none", tile, rows_per_strip, planar, predictor)
+    tiff_write.write_device(path, tensor, compress or "none", tile, rows_per_strip, planar, predictor,
+                            **_new_options(overviews, resampling, nodata, geo))
 
 
 def raster_size(path):

@@ -2,13 +2,15 @@
 parsed on the host and decompressed on the GPU: the ctypes binding of liblbdrn_tiff.so (include/lbdrn_tiff.h,
 csrc/tiff.hip, csrc/tiff.inc).  Built by csrc/build.py beside liblbdrn_hip.so; LBDRN_TIFF_LIB names another file.
 
-    parse(buf)                 the first IFD of a classic TIFF or BigTIFF, either byte order -> Scene (layout + segment table)
+    parse(buf, ifd=0)          an IFD of a classic TIFF or BigTIFF, either byte order -> Scene (layout + segment table)
+    read_ifds(buf)             the offsets of the IFD chain; overview_ifds(buf): the positions of the overview levels in it
+    read_geo_tags(buf)         the GeoTIFF and GDAL tags of the first IFD, verbatim, for tiff_write's `geo`
     read_device(path, device)  contiguous [C,H,W] tensor in HBM: int16 storage for 16-bit samples, like every plane of this
                                package, uint8 for 8-bit ones
     read(path, device)         numpy, with the conventions of raster_io._read_tiff ([H,W] for one band)
 
 Everything outside the subset raises ValueError naming the tag and value before any device work.  Georeferencing tags are
-ignored, as the reference's own writer drops them."""
+never interpreted: read_geo_tags copies them for a writer to carry over."""
 import ctypes
 import os
 import struct
@@ -80,7 +82,7 @@ def _check(rc, what):
 # type -> (struct code, bytes); 16-18 are BigTIFF's LONG8, SLONG8, IFD8
 _FIELD = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2), 9: ("i", 4),
           10: ("ii", 8), 11: ("f", 4), 12: ("d", 8), 13: ("I", 4), 16: ("Q", 8), 17: ("q", 8), 18: ("Q", 8)}
-_WANTED = {256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression", 273: "StripOffsets",
+_WANTED = {254: "NewSubfileType", 256: "ImageWidth", 257: "ImageLength", 258: "BitsPerSample", 259: "Compression", 273: "StripOffsets",
            277: "SamplesPerPixel", 278: "RowsPerStrip", 279: "StripByteCounts", 284: "PlanarConfiguration", 317: "Predictor",
            322: "TileWidth", 323: "TileLength", 324: "TileOffsets", 325: "TileByteCounts", 338: "ExtraSamples", 339: "SampleFormat"}
 
@@ -101,28 +103,68 @@ class Scene:
         return self.layout.compression == COMP_NONE and not self.layout.tiled
 
 
-def read_tags(buf, path="TIFF"):
-    """{tag: [values]} of the first IFD, the byte order mark ('<' or '>') and whether the file is a BigTIFF"""
+def _header(buf, path):
+    """(byte order mark, BigTIFF?, offset of the first IFD)"""
     bo = {b"II": "<", b"MM": ">"}.get(bytes(buf[:2]))
     if bo is None or len(buf) < 8:
         raise ValueError(f"{path}: not a TIFF (no II / MM byte order mark)")
     magic = struct.unpack_from(bo + "H", buf, 2)[0]
     if magic == 42:
-        big = False
-        off = struct.unpack_from(bo + "I", buf, 4)[0]
-    elif magic == 43:
-        big = True
+        return bo, False, struct.unpack_from(bo + "I", buf, 4)[0]
+    if magic == 43:
         if len(buf) < 16 or struct.unpack_from(bo + "HH", buf, 4) != (8, 0):
             raise ValueError(f"{path}: BigTIFF header with an offset size other than 8")
-        off = struct.unpack_from(bo + "Q", buf, 8)[0]
-    else:
-        raise ValueError(f"{path}: not a TIFF (magic {magic})")
+        return bo, True, struct.unpack_from(bo + "Q", buf, 8)[0]
+    raise ValueError(f"{path}: not a TIFF (magic {magic})")
+
+
+MAX_IFDS = 4096      # the chain is walked no further: a pyramid has some twenty levels
+
+
+def read_ifds(buf, path="TIFF"):
+    """The offsets of the file's IFDs in chain order.  ValueError for an IFD or a next-IFD field outside the file, for a chain
+    that comes back to an IFD it has visited, and for one longer than MAX_IFDS."""
+    bo, big, off = _header(buf, path)
+    cnt_fmt, cnt_size, ent, nxt_fmt, nxt_size = ("Q", 8, 20, "Q", 8) if big else ("H", 2, 12, "I", 4)
+    out, seen = [], set()
+    while off:
+        if off in seen:
+            raise ValueError(f"{path}: the IFD chain loops: IFD {len(out)} is at offset {off}, where an earlier one lies")
+        if len(out) >= MAX_IFDS:
+            raise ValueError(f"{path}: more than {MAX_IFDS} IFDs")
+        if off + cnt_size > len(buf):
+            raise ValueError(f"{path}: IFD {len(out)} (offset {off}) lies outside the file's {len(buf)} bytes")
+        n = struct.unpack_from(bo + cnt_fmt, buf, off)[0]
+        end = off + cnt_size + ent * n
+        if end + nxt_size > len(buf):
+            raise ValueError(f"{path}: IFD {len(out)} (offset {off}, {n} entries) lies outside the file's {len(buf)} bytes")
+        seen.add(off)
+        out.append(off)
+        off = struct.unpack_from(bo + nxt_fmt, buf, end)[0]
+    return out
+
+
+def _ifd_offset(buf, path, ifd):
+    """(byte order mark, BigTIFF?, offset of IFD number `ifd`, what to call it); ifd = 0 reads the header alone"""
+    bo, big, off = _header(buf, path)
+    if ifd == 0:
+        return bo, big, off, "the first IFD"
+    ifds = read_ifds(buf, path)
+    if not 0 <= ifd < len(ifds):
+        raise IndexError(f"{path}: IFD {ifd} of a file that has {len(ifds)}")
+    return bo, big, ifds[ifd], f"IFD {ifd}"
+
+
+def read_tags(buf, path="TIFF", ifd=0):
+    """{tag: [values]} of the first IFD (or of IFD number `ifd` of the chain), the byte order mark ('<' or '>') and whether
+    the file is a BigTIFF"""
+    bo, big, off, name = _ifd_offset(buf, path, ifd)
     cnt_fmt, cnt_size, ent, inline = ("Q", 8, 20, 8) if big else ("H", 2, 12, 4)
     if off + cnt_size > len(buf):
-        raise ValueError(f"{path}: the first IFD lies outside the file")
+        raise ValueError(f"{path}: {name} lies outside the file")
     n = struct.unpack_from(bo + cnt_fmt, buf, off)[0]
     if off + cnt_size + ent * n > len(buf):
-        raise ValueError(f"{path}: the first IFD lies outside the file")
+        raise ValueError(f"{path}: {name} lies outside the file")
     tags = {}
     for i in range(n):
         at = off + cnt_size + ent * i
@@ -143,9 +185,10 @@ def read_tags(buf, path="TIFF"):
     return tags, bo, big
 
 
-def parse(buf, path="TIFF"):
-    """Scene of the first IFD; ValueError naming the tag and value for everything outside the subset."""
-    tags, bo, _ = read_tags(buf, path)
+def parse(buf, path="TIFF", ifd=0):
+    """Scene of the first IFD, or of IFD number `ifd` of the chain (IndexError where the file has fewer); ValueError naming
+    the tag and value for everything outside the subset."""
+    tags, bo, _ = read_tags(buf, path, ifd)
 
     def one(tag, default=None):
         v = tags.get(tag)
@@ -206,6 +249,50 @@ def parse(buf, path="TIFF"):
     lay = Layout(C, H, W, bits[0], 1 if bo == ">" else 0, planar, sw, sh, 1 if tiled else 0,
                  COMP_DEFLATE if comp == COMP_DEFLATE_OLD else comp, pred)
     return Scene(lay, np.asarray(offsets, np.uint64), np.asarray(counts, np.uint64), fmt[0], bo)
+
+
+# ---------------------------------------------------------------- overviews and georeferencing tags
+
+def overview_ifds(buf, path="TIFF"):
+    """the chain positions of the file's overview levels: the IFDs whose NewSubfileType (254) has bit 0 set, in file order"""
+    out = []
+    for i in range(len(read_ifds(buf, path))):
+        if i and int(read_tags(buf, path, i)[0].get(254, [0])[0]) & 1:
+            out.append(i)
+    return out
+
+
+# ModelPixelScale, ModelTiepoint, ModelTransformation (DOUBLE), GeoKeyDirectory (SHORT), GeoDoubleParams (DOUBLE),
+# GeoAsciiParams, GDAL_METADATA, GDAL_NODATA (ASCII): tag -> (type, bytes of an element)
+GEO_TAGS = {33550: (12, 8), 33922: (12, 8), 34264: (12, 8), 34735: (3, 2), 34736: (12, 8), 34737: (2, 1), 42112: (2, 1), 42113: (2, 1)}
+
+
+def read_geo_tags(buf, path="TIFF"):
+    """The georeferencing tags of the first IFD as [(tag, type, count, value bytes)], the values little-endian whatever the
+    file's byte order: copied, never interpreted.  [] for a file that has none.  What tiff_write takes as `geo`."""
+    bo, big, off, name = _ifd_offset(buf, path, 0)
+    cnt_fmt, cnt_size, ent, inline = ("Q", 8, 20, 8) if big else ("H", 2, 12, 4)
+    if off + cnt_size > len(buf):
+        raise ValueError(f"{path}: {name} lies outside the file")
+    n = struct.unpack_from(bo + cnt_fmt, buf, off)[0]
+    if off + cnt_size + ent * n > len(buf):
+        raise ValueError(f"{path}: {name} lies outside the file")
+    out = []
+    for i in range(n):
+        at = off + cnt_size + ent * i
+        tag, typ = struct.unpack_from(bo + "HH", buf, at)
+        if tag not in GEO_TAGS or typ != GEO_TAGS[tag][0]:
+            continue
+        cnt = struct.unpack_from(bo + ("Q" if big else "I"), buf, at + 4)[0]
+        size = GEO_TAGS[tag][1]
+        val_at = at + 4 + (8 if big else 4)
+        if size * cnt > inline:
+            val_at = struct.unpack_from(bo + ("Q" if big else "I"), buf, val_at)[0]
+        if val_at + size * cnt > len(buf):
+            raise ValueError(f"{path}: the values of tag {tag} lie outside the file")
+        raw = np.frombuffer(buf, np.dtype(bo + "u%d" % size), cnt, val_at).astype("<u%d" % size).tobytes()
+        out.append((int(tag), int(typ), int(cnt), raw))
+    return out
 
 
 # ---------------------------------------------------------------- the host path of an oversize Deflate segment
@@ -305,10 +392,10 @@ def read_device(path, device=None):
         return read_device_bytes(f.read(), path, device)
 
 
-def read_device_bytes(buf, path, device=None):
-    """read_device of a file whose bytes the caller holds already"""
+def read_device_bytes(buf, path, device=None, ifd=0):
+    """read_device of a file whose bytes the caller holds already; ifd: the IFD of the chain to read"""
     import torch
-    scene = parse(buf, path)
+    scene = parse(buf, path, ifd)
     route = _over_cap(scene.layout, path)
     dev = _device(device)
     if route == "host":
@@ -318,11 +405,11 @@ def read_device_bytes(buf, path, device=None):
     return decode_device(buf, scene, dev)
 
 
-def read(path, device=None):
+def read(path, device=None, ifd=0):
     """numpy uint8 / uint16 [C,H,W], [H,W] for one band: what raster_io._read_tiff returns for the files it reads itself"""
     with open(path, "rb") as f:
         buf = f.read()
-    scene = parse(buf, path)
+    scene = parse(buf, path, ifd)
     if _over_cap(scene.layout, path) == "host":
         a = _read_host_deflate(buf, scene)
     else:
