@@ -1,4 +1,4 @@
-"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so, liblbdrn_tiffw.so, liblbdrn_quality.so and liblbdrn_pyramid.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so, liblbdrn_tiffw.so, liblbdrn_quality.so, liblbdrn_pyramid.so and liblbdrn_plane3.so for gfx950 with hipcc (in-tree, next to the Python host code).
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -184,6 +184,29 @@ def build_pyramid(force=False):
     return PYRAMID_OUT
 
 
+PLANE3_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_plane3.so")
+PLANE3_SRCS = ["plane3.hip"]
+PLANE3_DEPS = ["plane3.inc", "common.hpp", "exports_plane3.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_plane3.h"]
+
+
+def build_plane3(force=False):
+    """liblbdrn_plane3.so (include/lbdrn_plane3.h): the LBB3 coder and decoder of the MSB payload, a library of its own like
+    liblbdrn_pyramid.so -- same compiler, same flags, its own object file and version script."""
+    if not force and os.path.exists(PLANE3_OUT):
+        t = os.path.getmtime(PLANE3_OUT)
+        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in PLANE3_SRCS + PLANE3_DEPS + ["build.py"]):
+            return PLANE3_OUT
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = []
+    for src in PLANE3_SRCS:
+        obj = os.path.join(HERE, src.replace(".hip", ".o"))
+        objs.append(obj)
+        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
+    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
+                           "-Wl,--version-script=" + os.path.join(HERE, "exports_plane3.map"), "-o", PLANE3_OUT] + objs)
+    return PLANE3_OUT
+
+
 def stale():
     if not os.path.exists(OUT):
         return True
@@ -200,6 +223,7 @@ def build(force=False, extra=(), out=None):
         build_tiffw(force)
         build_quality(force)
         build_pyramid(force)
+        build_plane3(force)
     if out == OUT and not force and not stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -236,4 +260,5 @@ if __name__ == "__main__":
         print(TIFFW_OUT)
         print(QUALITY_OUT)
         print(PYRAMID_OUT)
+        print(PLANE3_OUT)
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

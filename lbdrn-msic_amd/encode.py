@@ -27,7 +27,8 @@ from LBDRNdataset import tile_windows
 DEVICE = "cuda:0"
 BASE_CODEC = os.environ.get("LBDRN_BASE_CODEC", "LBB2")   # "jp2": JPEG 2000 through OpenJPEG, what the reference writes;
                                                           # "jp2-gpu": the same format coded on the GPU (csrc/jp2k.hip)
-                                                          # (encode.py:137); "LBB1": the portable host payload of older files
+                                                          # (encode.py:137); "LBB1": the portable host payload of older files;
+                                                          # "LBB3": LBB2 with inter-band prediction (csrc/plane3.hip)
 REPORT_BOTH = os.environ.get("LBDRN_REPORT_BOTH_BPSP", "") not in ("", "0")   # also log the size of the payload format NOT
 # written (JPEG 2000 costs 2-3 s of one host core per 8 x 2048^2 tile: off by default)
 IN_FLIGHT = int(os.environ["LBDRN_IN_FLIGHT"]) if "LBDRN_IN_FLIGHT" in os.environ else None   # tiles of one image
@@ -107,7 +108,7 @@ def report_and_pack(args, res, base_ahead=None):
         t0 = time.time()
         base_payload = base_ahead()
         logger.log.info(f"MSB payload ({BASE_CODEC}) coded beside the fit; waited {time.time() - t0:.3f}s more for it")
-    elif BASE_CODEC == "LBB2" or BASE_CODEC.lower() == container.JP2_GPU_CODEC:   # coded from the plane in HBM
+    elif BASE_CODEC in ("LBB2", "LBB3") or BASE_CODEC.lower() == container.JP2_GPU_CODEC:   # coded from the plane in HBM
         base_payload = container.encode_base(res.msb_device, codec=BASE_CODEC, device=DEVICE, as_uint8=res.msb_max <= 255)
     else:
         base_payload = container.encode_base(_host_msb(res), codec=BASE_CODEC)

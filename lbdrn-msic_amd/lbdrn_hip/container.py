@@ -27,6 +27,8 @@ import numpy as np
 NN_PRIVATE_MAGIC = b"LBW1"
 BASE_PRIVATE_MAGIC = b"LBB1"
 BASE_LBB2_MAGIC = b"LBB2"
+BASE_LBB3_MAGIC = b"LBB3"
+LBB3_MAX_BANDS = 16
 
 
 # ---------------------------------------------------------------- header
@@ -308,7 +310,7 @@ JP2_GPU_CODEC = "jp2-gpu"                               # the same format, coded
 
 def check_base_codec(codec):
     """The MSB payload codec names encode_base takes; anything else is refused (ValueError) before any work is done."""
-    if codec.lower() in JP2_HOST_CODECS or codec.lower() == JP2_GPU_CODEC or codec in ("LBB2", "LBB1"):
+    if codec.lower() in JP2_HOST_CODECS or codec.lower() == JP2_GPU_CODEC or codec in ("LBB2", "LBB1", "LBB3"):
         return codec
     raise ValueError(f"unknown MSB payload codec {codec!r}")
 
@@ -323,7 +325,8 @@ def encode_base(msb, codec="LBB2", device="cuda:0", as_uint8=None):
     that only need to write small rasters.  jp2: a lossless JPEG 2000 file through OpenJPEG on the host.  jp2-gpu: the
     same format with the same coding parameters, wavelet and block coder on the GPU (lbdrn_jp2k_encode, csrc/jp2k.hip),
     from a numpy array or the device tensor like LBB2; decode_base reads either through OpenJPEG or the GPU decoder
-    (LBDRN_BASE_DECODER, _decode_jp2)."""
+    (LBDRN_BASE_DECODER, _decode_jp2).  LBB3: LBB2's entropy stage over units that hold all bands, each band predicted
+    spatially or from the band before's residual (lbdrn_plane3_encode, csrc/plane3.hip); at most 16 bands."""
     check_base_codec(codec)
     if codec.lower() == JP2_GPU_CODEC:
         from . import ops
@@ -349,6 +352,17 @@ def encode_base(msb, codec="LBB2", device="cuda:0", as_uint8=None):
             planes, code = msb, (1 if as_uint8 else 2)
         C, H, W = planes.shape
         return BASE_LBB2_MAGIC + struct.pack(">BHII", code, C, H, W) + ops.plane_encode(planes)
+    if codec == "LBB3":   # LBB2's frame around a body with inter-band prediction (lbdrn_hip/plane3.py, csrc/plane3.hip)
+        from . import ops, plane3
+        if msb.shape[0] > LBB3_MAX_BANDS:
+            raise ValueError(f"LBB3 codes at most {LBB3_MAX_BANDS} bands, the MSB planes have {msb.shape[0]}")
+        if isinstance(msb, np.ndarray):
+            code = 1 if msb.dtype == np.uint8 else 2
+            planes = ops.to_device_u16(np.ascontiguousarray(msb).astype(np.uint16), device)
+        else:
+            planes, code = msb, (1 if as_uint8 else 2)
+        C, H, W = planes.shape
+        return BASE_LBB3_MAGIC + struct.pack(">BHII", code, C, H, W) + plane3.encode(planes)
     if codec != "LBB1":
         raise ValueError(f"unknown MSB payload codec {codec!r}")
     msb = np.ascontiguousarray(msb)
@@ -405,7 +419,7 @@ def _decode_jp2(buf, device, keep_on_device):
 
 
 def decode_base(buf, device="cuda:0", keep_on_device=False):
-    """MSB payload -> [C,H,W] numpy (uint8 / uint16 as encoded).  keep_on_device: an LBB2 payload, and a JPEG 2000 payload
+    """MSB payload -> [C,H,W] numpy (uint8 / uint16 as encoded).  keep_on_device: an LBB2 or LBB3 payload, and a JPEG 2000 payload
     read by the GPU decoder, is returned as the device tensor it was decoded into (uint16 bits, int16 storage) --
     decode.py feeds it straight to the apply kernel."""
     from . import jp2
@@ -415,6 +429,14 @@ def decode_base(buf, device="cuda:0", keep_on_device=False):
         from . import ops
         code, C, H, W = struct.unpack_from(">BHII", buf, 4)
         planes = ops.plane_decode(bytes(buf[15:]), C, H, W, device)
+        if keep_on_device:
+            return planes
+        x = ops.from_device_u16(planes)
+        return x.astype(np.uint8) if code == 1 else x
+    if buf[:4] == BASE_LBB3_MAGIC:
+        from . import ops, plane3
+        code, C, H, W = struct.unpack_from(">BHII", buf, 4)
+        planes = plane3.decode(bytes(buf[15:]), C, H, W, device)
         if keep_on_device:
             return planes
         x = ops.from_device_u16(planes)
