@@ -1,4 +1,5 @@
-"""Build liblbdrn_hip.so, liblbdrn_jp2k_dec.so, liblbdrn_resid.so, liblbdrn_tiff.so, liblbdrn_tiffw.so, liblbdrn_quality.so, liblbdrn_pyramid.so and liblbdrn_plane3.so for gfx950 with hipcc (in-tree, next to the Python host code).
+"""Build the HIP libraries of LIBS -- liblbdrn_hip.so and the libraries beside it -- for gfx950 with hipcc (in-tree, next
+to the Python host code), and the optional OpenJPEG shim liblbdrn_jp2.so with gcc.
 
     python lbdrn-msic_amd/csrc/build.py [--force]
 
@@ -7,19 +8,41 @@ must not invent more.  -fhip-fp32-correctly-rounded-divide-sqrt: IEEE division f
 normalisation p = msb/max and the sigmoid (the reference divides in numpy / torch float32).
 """
 import os
+import re
 import subprocess
 import sys
+import threading
+from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = ["cabi.hip", "generic.hip", "apply_mfma.hip", "train_mfma.hip", "randperm.hip", "plane_codec.hip", "weights_codec.hip", "jp2k.hip"]
-HDRS = sorted(f for f in os.listdir(HERE) if f.endswith((".hpp", ".inc"))) + ["exports.map", "../../include/lbdrn_hip.h"]
-OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wall", "-Wno-unused-function",
-         "-fvisibility=hidden"]   # the exports are the functions include/lbdrn_hip.h declares, nothing else
+         "-fvisibility=hidden"]   # the exports are the functions the library's header declares, nothing else
+
+# One entry per HIP library: liblbdrn_<stem>.so is linked from the objects of `srcs` with the version script `script` and
+# exports what include/<header> declares.  Every library has the same compiler and flags and its own object files.  The
+# first entry is the main library; it alone takes build()'s `extra` flags and `out` override.
+LIBS = [
+    dict(stem="hip", header="lbdrn_hip.h", script="exports.map",
+         srcs=["cabi.hip", "generic.hip", "apply_mfma.hip", "train_mfma.hip", "randperm.hip", "plane_codec.hip", "weights_codec.hip",
+               "jp2k.hip"]),
+    dict(stem="jp2k_dec", header="lbdrn_jp2k_dec.h", script="exports_jp2k_dec.map", srcs=["jp2k_dec.hip"]),   # JPEG 2000 decoder
+    dict(stem="resid", header="lbdrn_resid.h", script="exports_resid.map", srcs=["resid.hip"]),               # residual layer
+    dict(stem="tiff", header="lbdrn_tiff.h", script="exports_tiff.map", srcs=["tiff.hip"]),                   # TIFF reader
+    dict(stem="tiffw", header="lbdrn_tiff_write.h", script="exports_tiffw.map", srcs=["tiffw.hip"]),          # TIFF writer
+    dict(stem="quality", header="lbdrn_quality.h", script="exports_quality.map", srcs=["quality.hip"]),       # quality report
+    dict(stem="pyramid", header="lbdrn_pyramid.h", script="exports_pyramid.map", srcs=["pyramid.hip"]),       # overview levels
+    dict(stem="plane3", header="lbdrn_plane3.h", script="exports_plane3.map", srcs=["plane3.hip"]),           # LBB3 MSB payload
+]
 
 
+def output(lib):
+    return os.path.join(os.path.dirname(HERE), f"liblbdrn_{lib['stem']}.so")
+
+
+OUT = output(LIBS[0])
 JP2_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_jp2.so")
+_COMPILERS = threading.BoundedSemaphore(16)   # compiler processes at once, however many libraries the table has
 
 
 def build_jp2(force=False):
@@ -44,204 +67,53 @@ def build_jp2(force=False):
     return None
 
 
-JP2K_DEC_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_jp2k_dec.so")
-JP2K_DEC_SRCS = ["jp2k_dec.hip"]
-JP2K_DEC_DEPS = ["jp2k_t1.inc", "jp2k_t2.inc", "jp2k_t1d.inc", "jp2k_t2d.inc", "common.hpp", "exports_jp2k_dec.map",
-                 "../../include/lbdrn_hip.h", "../../include/lbdrn_jp2k_dec.h"]
+def deps(lib):
+    """The files a library is built from: its sources, everything they reach through #include "..." lines (resolved beside
+    the including file; <...> includes belong to the toolchain), its version script and this file."""
+    found, todo = set(), [os.path.join(HERE, f) for f in lib["srcs"]]
+    while todo:
+        path = os.path.normpath(todo.pop())
+        if path not in found:
+            found.add(path)
+            with open(path) as f:
+                todo += [os.path.join(os.path.dirname(path), inc) for inc in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', f.read(), re.M)]
+    return found | {os.path.join(HERE, lib["script"]), os.path.join(HERE, "build.py")}
 
 
-def build_jp2k_dec(force=False):
-    """liblbdrn_jp2k_dec.so (include/lbdrn_jp2k_dec.h): the GPU decoder of the JPEG 2000 payload, a library of its own
-    beside liblbdrn_hip.so -- same compiler, same flags, its own object files and version script."""
-    if not force and os.path.exists(JP2K_DEC_OUT):
-        t = os.path.getmtime(JP2K_DEC_OUT)
-        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in JP2K_DEC_SRCS + JP2K_DEC_DEPS + ["build.py"]):
-            return JP2K_DEC_OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    for src in JP2K_DEC_SRCS:
-        obj = os.path.join(HERE, src.replace(".hip", ".o"))
-        objs.append(obj)
-        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-                           "-Wl,--version-script=" + os.path.join(HERE, "exports_jp2k_dec.map"), "-o", JP2K_DEC_OUT] + objs)
-    return JP2K_DEC_OUT
-
-
-RESID_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_resid.so")
-RESID_SRCS = ["resid.hip"]
-RESID_DEPS = ["resid.inc", "common.hpp", "exports_resid.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_resid.h"]
-
-
-def build_resid(force=False):
-    """liblbdrn_resid.so (include/lbdrn_resid.h): the residual layer's coder and decoder, a library of its own like
-    liblbdrn_jp2k_dec.so -- same compiler, same flags, its own object file and version script."""
-    if not force and os.path.exists(RESID_OUT):
-        t = os.path.getmtime(RESID_OUT)
-        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in RESID_SRCS + RESID_DEPS + ["build.py"]):
-            return RESID_OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    for src in RESID_SRCS:
-        obj = os.path.join(HERE, src.replace(".hip", ".o"))
-        objs.append(obj)
-        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-                           "-Wl,--version-script=" + os.path.join(HERE, "exports_resid.map"), "-o", RESID_OUT] + objs)
-    return RESID_OUT
-
-
-TIFF_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_tiff.so")
-TIFF_SRCS = ["tiff.hip"]
-TIFF_DEPS = ["tiff.inc", "common.hpp", "exports_tiff.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_tiff.h"]
-
-
-def build_tiff(force=False):
-    """liblbdrn_tiff.so (include/lbdrn_tiff.h): the TIFF reader's segment decoders and placement, a library of its own
-    like liblbdrn_resid.so -- same compiler, same flags, its own object file and version script."""
-    if not force and os.path.exists(TIFF_OUT):
-        t = os.path.getmtime(TIFF_OUT)
-        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in TIFF_SRCS + TIFF_DEPS + ["build.py"]):
-            return TIFF_OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    for src in TIFF_SRCS:
-        obj = os.path.join(HERE, src.replace(".hip", ".o"))
-        objs.append(obj)
-        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-                           "-Wl,--version-script=" + os.path.join(HERE, "exports_tiff.map"), "-o", TIFF_OUT] + objs)
-    return TIFF_OUT
-
-
-TIFFW_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_tiffw.so")
-TIFFW_SRCS = ["tiffw.hip"]
-TIFFW_DEPS = ["tiffw.inc", "tiff.inc", "common.hpp", "exports_tiffw.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_tiff.h",
-              "../../include/lbdrn_tiff_write.h"]
-
-
-def build_tiffw(force=False):
-    """liblbdrn_tiffw.so (include/lbdrn_tiff_write.h): the TIFF writer's gather, Deflate encoder and packing, a library of
-    its own like liblbdrn_tiff.so -- same compiler, same flags, its own object file and version script."""
-    if not force and os.path.exists(TIFFW_OUT):
-        t = os.path.getmtime(TIFFW_OUT)
-        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in TIFFW_SRCS + TIFFW_DEPS + ["build.py"]):
-            return TIFFW_OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    for src in TIFFW_SRCS:
-        obj = os.path.join(HERE, src.replace(".hip", ".o"))
-        objs.append(obj)
-        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-                           "-Wl,--version-script=" + os.path.join(HERE, "exports_tiffw.map"), "-o", TIFFW_OUT] + objs)
-    return TIFFW_OUT
-
-
-QUALITY_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_quality.so")
-QUALITY_SRCS = ["quality.hip"]
-QUALITY_DEPS = ["quality.inc", "common.hpp", "exports_quality.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_quality.h"]
-
-
-def build_quality(force=False):
-    """liblbdrn_quality.so (include/lbdrn_quality.h): the comparison of two rasters in HBM -- error statistics, SSIM and SAM --
-    a library of its own like liblbdrn_tiffw.so -- same compiler, same flags, its own object file and version script."""
-    if not force and os.path.exists(QUALITY_OUT):
-        t = os.path.getmtime(QUALITY_OUT)
-        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in QUALITY_SRCS + QUALITY_DEPS + ["build.py"]):
-            return QUALITY_OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    for src in QUALITY_SRCS:
-        obj = os.path.join(HERE, src.replace(".hip", ".o"))
-        objs.append(obj)
-        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-                           "-Wl,--version-script=" + os.path.join(HERE, "exports_quality.map"), "-o", QUALITY_OUT] + objs)
-    return QUALITY_OUT
-
-
-PYRAMID_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_pyramid.so")
-PYRAMID_SRCS = ["pyramid.hip"]
-PYRAMID_DEPS = ["pyramid.inc", "common.hpp", "exports_pyramid.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_pyramid.h"]
-
-
-def build_pyramid(force=False):
-    """liblbdrn_pyramid.so (include/lbdrn_pyramid.h): the overview levels of a raster in HBM, a library of its own like
-    liblbdrn_quality.so -- same compiler, same flags, its own object file and version script."""
-    if not force and os.path.exists(PYRAMID_OUT):
-        t = os.path.getmtime(PYRAMID_OUT)
-        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in PYRAMID_SRCS + PYRAMID_DEPS + ["build.py"]):
-            return PYRAMID_OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    for src in PYRAMID_SRCS:
-        obj = os.path.join(HERE, src.replace(".hip", ".o"))
-        objs.append(obj)
-        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-                           "-Wl,--version-script=" + os.path.join(HERE, "exports_pyramid.map"), "-o", PYRAMID_OUT] + objs)
-    return PYRAMID_OUT
-
-
-PLANE3_OUT = os.path.join(os.path.dirname(HERE), "liblbdrn_plane3.so")
-PLANE3_SRCS = ["plane3.hip"]
-PLANE3_DEPS = ["plane3.inc", "common.hpp", "exports_plane3.map", "../../include/lbdrn_hip.h", "../../include/lbdrn_plane3.h"]
-
-
-def build_plane3(force=False):
-    """liblbdrn_plane3.so (include/lbdrn_plane3.h): the LBB3 coder and decoder of the MSB payload, a library of its own like
-    liblbdrn_pyramid.so -- same compiler, same flags, its own object file and version script."""
-    if not force and os.path.exists(PLANE3_OUT):
-        t = os.path.getmtime(PLANE3_OUT)
-        if not any(os.path.getmtime(os.path.join(HERE, f)) > t for f in PLANE3_SRCS + PLANE3_DEPS + ["build.py"]):
-            return PLANE3_OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    for src in PLANE3_SRCS:
-        obj = os.path.join(HERE, src.replace(".hip", ".o"))
-        objs.append(obj)
-        subprocess.check_call([hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + ["-o", obj, os.path.join(HERE, src)])
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC",
-                           "-Wl,--version-script=" + os.path.join(HERE, "exports_plane3.map"), "-o", PLANE3_OUT] + objs)
-    return PLANE3_OUT
+def _stale(lib, out):
+    return not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in deps(lib))
 
 
 def stale():
-    if not os.path.exists(OUT):
-        return True
-    t = os.path.getmtime(OUT)
-    return any(os.path.getmtime(os.path.join(HERE, f)) > t for f in SRCS + HDRS + ["build.py"])
+    return _stale(LIBS[0], OUT)
+
+
+def _run(cmd):
+    with _COMPILERS:
+        subprocess.check_call(cmd)
+
+
+def build_lib(lib, force=False, extra=(), out=None):
+    """One entry of LIBS: nothing if `out` is newer than deps(lib), else its sources compiled side by side and linked."""
+    out = out or output(lib)
+    tag = "" if out == output(lib) else "." + os.path.basename(out)[len(f"liblbdrn_{lib['stem']}_"):-len(".so")]   # objects per variant
+    if not force and not _stale(lib, out):
+        return out
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    objs = [os.path.join(HERE, src.replace(".hip", tag + ".o")) for src in lib["srcs"]]
+    with ThreadPoolExecutor(len(objs)) as pool:
+        list(pool.map(_run, [[hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + list(extra) + ["-o", obj, os.path.join(HERE, src)]
+                             for src, obj in zip(lib["srcs"], objs)]))
+    _run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(HERE, lib["script"]), "-o", out] + objs)
+    return out
 
 
 def build(force=False, extra=(), out=None):
-    out = out or OUT
-    if out == OUT:
-        build_jp2k_dec(force)
-        build_resid(force)
-        build_tiff(force)
-        build_tiffw(force)
-        build_quality(force)
-        build_pyramid(force)
-        build_plane3(force)
-    if out == OUT and not force and not stale():
-        return OUT
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    procs = []
-    for src in SRCS:
-        tag = "" if out == OUT else "." + os.path.basename(out)[len("liblbdrn_hip_"):-len(".so")]   # objects per variant
-        obj = os.path.join(HERE, src.replace(".hip", tag + ".o"))
-        objs.append(obj)
-        cmd = [hipcc, "-c"] + [f for f in FLAGS if f != "-shared"] + list(extra) + \
-              ["-o", obj, os.path.join(HERE, src)]
-        procs.append((src, subprocess.Popen(cmd)))
-    for src, p in procs:
-        if p.wait() != 0:
-            raise RuntimeError(f"hipcc failed on {src}")
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--version-script=" + os.path.join(HERE, "exports.map"),
-                           "-o", out] + objs)
-    return out
+    """Every library of LIBS, side by side; or, with `out`, that variant of the main library alone (always rebuilt)."""
+    if out and out != OUT:
+        return build_lib(LIBS[0], True, extra, out)
+    with ThreadPoolExecutor(len(LIBS)) as pool:
+        return list(pool.map(lambda lib: build_lib(lib, force, extra if lib is LIBS[0] else ()), LIBS))[0]
 
 
 if __name__ == "__main__":
@@ -254,11 +126,6 @@ if __name__ == "__main__":
                     out=os.path.join(os.path.dirname(HERE), f"liblbdrn_hip_{sys.argv[k + 1]}.so")))
     else:
         print(build(force="--force" in sys.argv))
-        print(JP2K_DEC_OUT)
-        print(RESID_OUT)
-        print(TIFF_OUT)
-        print(TIFFW_OUT)
-        print(QUALITY_OUT)
-        print(PYRAMID_OUT)
-        print(PLANE3_OUT)
+        for lib in LIBS[1:]:
+            print(output(lib))
         print(build_jp2(force="--force" in sys.argv) or "liblbdrn_jp2.so: OpenJPEG not found, not built")

@@ -5,7 +5,6 @@
 #include "common.hpp"
 
 namespace lbdrn {
-const char* last_error();
 bool mfma_train_supported(const lbdrn_geom& g, const lbdrn_net& net, int bs = 0);
 int mfma_train_step_features(const lbdrn_geom& g, const lbdrn_net& net);
 bool mfma_train_takes_groups(const lbdrn_geom& g, const lbdrn_net& net);

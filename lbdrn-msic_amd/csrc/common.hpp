@@ -10,7 +10,8 @@
 
 namespace lbdrn {
 
-void set_error(const char* fmt, ...);
+void set_error(const char* fmt, ...);   // error_buffer.inc: one buffer per shared library
+const char* last_error();
 
 #define LBDRN_HIP_TRY(expr)                                                                  \
     do {                                                                                     \

@@ -23,26 +23,13 @@
 // A chain that ends in a part-filled 16-wide k-tile runs on through fmaf(0, 0, acc) (the zero padding of the tile),
 // which turns an accumulator of -0.0f into +0.0f.  -ffp-contract=off and correctly rounded division / sqrt
 // (csrc/build.py) keep every other operation the one that is written.
-#include <stdarg.h>
-
 #include <cmath>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "lbdrn_math.hpp"
 
 namespace lbdrn {
-
-// ------------------------------------------------------------------ error string
-
-static thread_local char g_err[512] = "";
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-}
-const char* last_error() { return g_err; }
 
 int check_geom(const lbdrn_geom* g)
 {

@@ -27,21 +27,12 @@
 #include <vector>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "../../include/lbdrn_jp2k_dec.h"
 #include "jp2k_t1d.inc"
 #include "jp2k_t2d.inc"
 
 namespace lbdrn {
-
-static thread_local char g_jp2kd_error[512] = "";
-
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_jp2kd_error, sizeof(g_jp2kd_error), fmt, ap);
-    va_end(ap);
-}
 
 struct Jp2kdBlock {    // what the device needs of a code block (32 bytes)
     uint64_t offset;   // of its bytes in the file
@@ -280,7 +271,7 @@ static int jp2kd_decode(const void* buf, size_t n, uint16_t* planes, int C, int 
 
 extern "C" {
 
-const char* lbdrn_jp2kd_last_error(void) { return lbdrn::g_jp2kd_error; }
+const char* lbdrn_jp2kd_last_error(void) { return lbdrn::last_error(); }
 int lbdrn_jp2kd_abi_version(void) { return LBDRN_JP2KD_ABI_VERSION; }
 
 int lbdrn_jp2kd_info(const void* buf, size_t n, int32_t* C, int32_t* H, int32_t* W, int32_t* bits)

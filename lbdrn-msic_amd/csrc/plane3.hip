@@ -16,24 +16,14 @@
 //   k_p3_decode    one wave per unit: head and mode words, the unit's next words and the two windows in LDS, the
 //                  anti-diagonal walk with a ballot + mbcnt hand-out per step; the last row of every band is kept in LDS for
 //                  the next pass.
-#include <stdarg.h>
 #include <string.h>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "../../include/lbdrn_plane3.h"
 #include "plane3.inc"
 
 namespace lbdrn {
-
-static thread_local char g_plane3_error[512] = "";
-
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_plane3_error, sizeof(g_plane3_error), fmt, ap);
-    va_end(ap);
-}
 
 constexpr int P3_T = plane3::T;
 constexpr int P3_SCAN_THREADS = 256;
@@ -439,7 +429,7 @@ static int p3_decode(const void* body, size_t n, int C, int H, int W, int S, uin
 
 extern "C" {
 
-const char* lbdrn_plane3_last_error(void) { return lbdrn::g_plane3_error; }
+const char* lbdrn_plane3_last_error(void) { return lbdrn::last_error(); }
 int lbdrn_plane3_abi_version(void) { return LBDRN_PLANE3_ABI_VERSION; }
 
 size_t lbdrn_plane3_bound(int32_t C, int32_t H, int32_t W)

@@ -9,24 +9,14 @@
 //                  addresses on 16 bytes and the destination on 8; a lane for which one of them fails -- a row's tail, an
 //                  odd width, a window of a scene -- goes sample by sample through pyramid::reduce_at, which reads nothing
 //                  outside the level.  No LDS, no workspace; level k reads level k - 1 out of the output of the launch before.
-#include <stdarg.h>
 #include <string.h>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "../../include/lbdrn_pyramid.h"
 #include "pyramid.inc"
 
 namespace lbdrn {
-
-static thread_local char g_pyr_error[512] = "";
-
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_pyr_error, sizeof(g_pyr_error), fmt, ap);
-    va_end(ap);
-}
 
 constexpr int PT = 256;      // threads of a workgroup
 
@@ -155,7 +145,7 @@ static int pyr_build(const lbdrn_pyr_desc* d, const void* src, int levels, void*
 
 extern "C" {
 
-const char* lbdrn_pyr_last_error(void) { return lbdrn::g_pyr_error; }
+const char* lbdrn_pyr_last_error(void) { return lbdrn::last_error(); }
 int lbdrn_pyr_abi_version(void) { return LBDRN_PYR_ABI_VERSION; }
 
 int lbdrn_pyr_level_count(int32_t H, int32_t W, int32_t stop)

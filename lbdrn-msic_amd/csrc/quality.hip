@@ -17,24 +17,14 @@
 //                     workspace.
 //   k_quality_finish  one workgroup per band and one for the pixel record: n, ssim_n, and the float64 partial sums added in
 //                     a fixed order (lane t takes partials t, t + 256, ...; then a tree over the 256 lanes).
-#include <stdarg.h>
 #include <string.h>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "../../include/lbdrn_quality.h"
 #include "quality.inc"
 
 namespace lbdrn {
-
-static thread_local char g_quality_error[512] = "";
-
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_quality_error, sizeof(g_quality_error), fmt, ap);
-    va_end(ap);
-}
 
 constexpr int QT = 256;      // threads of every workgroup here
 
@@ -430,7 +420,7 @@ static int quality_compare(const void* a, int64_t a_row, int64_t a_plane, const 
 
 extern "C" {
 
-const char* lbdrn_quality_last_error(void) { return lbdrn::g_quality_error; }
+const char* lbdrn_quality_last_error(void) { return lbdrn::last_error(); }
 int lbdrn_quality_abi_version(void) { return LBDRN_QUALITY_ABI_VERSION; }
 
 size_t lbdrn_quality_result_bytes(int32_t C) { return C >= 1 && C <= quality::MAX_BANDS ? quality::result_bytes(C) : 0; }

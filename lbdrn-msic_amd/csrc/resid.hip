@@ -19,26 +19,16 @@
 //                    the block's bytes; the lanes whose rows the rectangle takes decode alone (RowReader never reads
 //                    outside the block), chunk by chunk through the same LDS tile, and the wave applies
 //                    recon' = clamp(recon + q (2 tau + 1)) to the rectangle's samples with coalesced row accesses.
-#include <stdarg.h>
 #include <string.h>
 
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "../../include/lbdrn_resid.h"
 #include "resid.inc"
 
 namespace lbdrn {
-
-static thread_local char g_resid_error[512] = "";
-
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_resid_error, sizeof(g_resid_error), fmt, ap);
-    va_end(ap);
-}
 
 constexpr int RS_CHUNK = 64;               // columns staged at a time
 constexpr int RS_PITCH = RS_CHUNK + 1;     // words per LDS row
@@ -317,7 +307,7 @@ static int resid_decode(const void* body, size_t n, int C, int H, int W, int x0,
 
 extern "C" {
 
-const char* lbdrn_resid_last_error(void) { return lbdrn::g_resid_error; }
+const char* lbdrn_resid_last_error(void) { return lbdrn::last_error(); }
 int lbdrn_resid_abi_version(void) { return LBDRN_RESID_ABI_VERSION; }
 
 size_t lbdrn_resid_bound(int32_t C, int32_t H, int32_t W)

@@ -13,24 +13,14 @@
 //                     prefix sum per sample channel (64 samples a step, the carry in the last lane), edge tiles cropped,
 //                     and one coalesced store per channel and step into planes[C][H][W].  Uncompressed segments are read
 //                     from the file itself; a byte count short of the segment is status 1.
-#include <stdarg.h>
 #include <string.h>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "../../include/lbdrn_tiff.h"
 #include "tiff.inc"
 
 namespace lbdrn {
-
-static thread_local char g_tiff_error[512] = "";
-
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_tiff_error, sizeof(g_tiff_error), fmt, ap);
-    va_end(ap);
-}
 
 struct TiffWs {
     uint64_t* offsets;   // [nseg]
@@ -178,7 +168,7 @@ static int tiff_decode(const lbdrn_tiff_layout* L, const void* file, size_t file
 
 extern "C" {
 
-const char* lbdrn_tiff_last_error(void) { return lbdrn::g_tiff_error; }
+const char* lbdrn_tiff_last_error(void) { return lbdrn::last_error(); }
 int lbdrn_tiff_abi_version(void) { return LBDRN_TIFF_ABI_VERSION; }
 
 size_t lbdrn_tiff_segment_count(const lbdrn_tiff_layout* layout)

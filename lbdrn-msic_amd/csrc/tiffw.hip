@@ -12,26 +12,16 @@
 //                     lengths, the three costs, then 64 tokens a step through a prefix sum of their bit lengths into LDS
 //                     words and from there to the segment's output slot.  counts[s] receives the stream's size.
 //   k_tiffw_pack      after rocprim's exclusive scan of counts into offsets: each slot copied to its place, and the total.
-#include <stdarg.h>
 #include <string.h>
 
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "error_buffer.inc"
 #include "../../include/lbdrn_tiff_write.h"
 #include "tiffw.inc"
 
 namespace lbdrn {
-
-static thread_local char g_tiffw_error[512] = "";
-
-void set_error(const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_tiffw_error, sizeof(g_tiffw_error), fmt, ap);
-    va_end(ap);
-}
 
 struct TiffwWs {
     uint8_t* raw;        // [nseg][pitch]: the segments' byte images
@@ -166,7 +156,7 @@ static int tiffw_encode(const lbdrn_tiffw_layout* L, const void* planes, void* o
 
 extern "C" {
 
-const char* lbdrn_tiffw_last_error(void) { return lbdrn::g_tiffw_error; }
+const char* lbdrn_tiffw_last_error(void) { return lbdrn::last_error(); }
 int lbdrn_tiffw_abi_version(void) { return LBDRN_TIFFW_ABI_VERSION; }
 
 size_t lbdrn_tiffw_segment_count(const lbdrn_tiffw_layout* layout)

@@ -1,10 +1,7 @@
 """ctypes binding of liblbdrn_hip.so (C ABI: include/lbdrn_hip.h)."""
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# LBDRN_HIP_LIB selects another build of the same ABI (e.g. the diagnostic liblbdrn_hip_stamps.so)
-_LIB_PATH = os.environ.get("LBDRN_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_hip.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library  # noqa: F401  (enum lbdrn_status)
 
 ABI_VERSION = 2           # LBDRN_ABI_VERSION of include/lbdrn_hip.h this binding was written against
 PATH_AUTO, PATH_GENERIC, PATH_MFMA = 0, 1, 2
@@ -17,9 +14,6 @@ TRAIN_ALONE = 0x800       # hint OR'ed into `path` of lbdrn_train_epoch: nothing
 class LbdrnError(RuntimeError):
     """A failed library call; `code` is the lbdrn_status it returned (None for host-side failures)."""
     code = None
-
-
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4   # enum lbdrn_status
 
 
 class Geom(ctypes.Structure):
@@ -88,38 +82,28 @@ SIGNATURES = {
                                         _vp, _vp, _sz, _vp]),
 }
 
-_lib = None
+# LBDRN_HIP_LIB selects another build of the same ABI (e.g. the diagnostic liblbdrn_hip_stamps.so)
+_NATIVE = Library("liblbdrn_hip.so", "LBDRN_HIP_LIB", "lbdrn_", ABI_VERSION, SIGNATURES, LbdrnError,
+                  missing="{path} is missing: build it with `python lbdrn-msic_amd/csrc/build.py` "
+                          "(hipcc, gfx950).  This package has no CPU fallback.",
+                  mismatch="liblbdrn_hip ABI {got} != {want}")
 
 
 def lib_path():
-    return _LIB_PATH
+    return _NATIVE.path
 
 
 def lib():
     """Load liblbdrn_hip.so.  torch must be imported first so that the HIP runtime torch ships
     (same SONAME, libamdhip64.so.7) is the one both sides use."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(_LIB_PATH):
-        raise LbdrnError(
-            f"{_LIB_PATH} is missing: build it with `python lbdrn-msic_amd/csrc/build.py` "
-            "(hipcc, gfx950).  This package has no CPU fallback.")
-    import torch  # noqa: F401  (loads libamdhip64 first)
-    L = ctypes.CDLL(_LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(L, name)  # AttributeError = ABI mismatch: fail loudly
-        fn.restype = res
-        fn.argtypes = args
-    if L.lbdrn_abi_version() != ABI_VERSION:
-        raise LbdrnError(f"liblbdrn_hip ABI {L.lbdrn_abi_version()} != {ABI_VERSION}")
-    _lib = L
-    return L
+    if _NATIVE.loaded is None:
+        import torch  # noqa: F401  (loads libamdhip64 first)
+        _NATIVE.lib()
+    return _NATIVE.loaded
 
 
 def check(rc):
     if rc != 0:
-        msg = lib().lbdrn_last_error()
-        err = LbdrnError(f"liblbdrn_hip error {rc}: {msg.decode() if msg else ''}")
+        err = LbdrnError(f"liblbdrn_hip error {rc}: {_NATIVE.last_error()}")
         err.code = rc
         raise err

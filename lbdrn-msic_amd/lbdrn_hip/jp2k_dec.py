@@ -4,61 +4,38 @@ without OpenJPEG, and leaves the planes in HBM.  Files with a precinct partition
 reversible component transform (mct = 1 on three components or more) are read as well.  Built by csrc/build.py beside liblbdrn_hip.so; LBDRN_JP2K_DEC_LIB
 names another file."""
 import ctypes
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PATH = os.environ.get("LBDRN_JP2K_DEC_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_jp2k_dec.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library, NativeError  # noqa: F401
+
 ABI_VERSION = 1
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
 MAX_SAMPLES = 1 << 33
 
-_lib = None
 
-
-class Jp2kDecError(RuntimeError):
-    def __init__(self, message, status=None):
-        super().__init__(message)
-        self.status = status
+class Jp2kDecError(NativeError):
+    pass
 
 
 class Jp2kDecUnsupported(Jp2kDecError):
     """the file is a JPEG 2000 stream this decoder does not take (LBDRN_E_UNSUPPORTED); the message names the feature"""
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_PATH):
-            raise Jp2kDecError(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
-        L = ctypes.CDLL(_PATH)
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        L.lbdrn_jp2kd_last_error.restype = ctypes.c_char_p
-        L.lbdrn_jp2kd_abi_version.restype = ctypes.c_int
-        L.lbdrn_jp2kd_info.argtypes = [ctypes.c_char_p, ctypes.c_size_t, i32p, i32p, i32p, i32p]
-        L.lbdrn_jp2kd_workspace.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
-        L.lbdrn_jp2kd_workspace.restype = ctypes.c_size_t
-        L.lbdrn_jp2kd_decode.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
-        if L.lbdrn_jp2kd_abi_version() != ABI_VERSION:
-            raise Jp2kDecError(f"{_PATH}: ABI version {L.lbdrn_jp2kd_abi_version()}, this binding is for {ABI_VERSION}")
-        _lib = L
-    return _lib
-
-
-def available():
-    try:
-        lib()
-        return True
-    except (Jp2kDecError, OSError):
-        return False
+_i32, _vp, _sz, _buf, _i32p = ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int32)
+SIGNATURES = {      # name -> (restype, argtypes): every function of include/lbdrn_jp2k_dec.h
+    "lbdrn_jp2kd_last_error": (ctypes.c_char_p, []),
+    "lbdrn_jp2kd_abi_version": (ctypes.c_int, []),
+    "lbdrn_jp2kd_info": (ctypes.c_int, [_buf, _sz, _i32p, _i32p, _i32p, _i32p]),
+    "lbdrn_jp2kd_workspace": (_sz, [_buf, _sz]),
+    "lbdrn_jp2kd_decode": (ctypes.c_int, [_buf, _sz, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+}
+_NATIVE = Library("liblbdrn_jp2k_dec.so", "LBDRN_JP2K_DEC_LIB", "lbdrn_jp2kd_", ABI_VERSION, SIGNATURES, Jp2kDecError)
+lib, available, _PATH = _NATIVE.lib, _NATIVE.available, _NATIVE.path
 
 
 def _check(rc, what):
     if rc != 0:
-        msg = f"{what}: {(lib().lbdrn_jp2kd_last_error() or b'').decode(errors='replace')}"
-        raise (Jp2kDecUnsupported if rc == E_UNSUPPORTED else Jp2kDecError)(msg, rc)
+        raise (Jp2kDecUnsupported if rc == E_UNSUPPORTED else Jp2kDecError)(f"{what}: {_NATIVE.last_error()}", rc)
 
 
 def info(buf):

@@ -2,56 +2,30 @@
 prediction, coded and decoded on the GPU (csrc/plane3.hip, csrc/plane3.inc).  Built by csrc/build.py beside
 liblbdrn_hip.so; LBDRN_PLANE3_LIB names another file."""
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PATH = os.environ.get("LBDRN_PLANE3_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_plane3.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library, NativeError  # noqa: F401
+
 ABI_VERSION = 1
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
 MAX_BANDS = 16
 
-_lib = None
+
+class Plane3Error(NativeError):
+    pass
 
 
-class Plane3Error(RuntimeError):
-    def __init__(self, message, status=None):
-        super().__init__(message)
-        self.status = status
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_PATH):
-            raise Plane3Error(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
-        L = ctypes.CDLL(_PATH)
-        i32, vp, sz = ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        L.lbdrn_plane3_last_error.restype = ctypes.c_char_p
-        L.lbdrn_plane3_abi_version.restype = ctypes.c_int
-        for name in ("lbdrn_plane3_bound", "lbdrn_plane3_encode_workspace", "lbdrn_plane3_decode_workspace"):
-            getattr(L, name).argtypes = [i32, i32, i32]
-            getattr(L, name).restype = sz
-        L.lbdrn_plane3_encode.argtypes = [vp, i32, i32, i32, vp, sz, vp, vp, sz, vp]
-        L.lbdrn_plane3_info.argtypes = [ctypes.c_char_p, sz, i32p, i32p, i32p, i32p]
-        L.lbdrn_plane3_decode.argtypes = [vp, sz, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-        if L.lbdrn_plane3_abi_version() != ABI_VERSION:
-            raise Plane3Error(f"{_PATH}: ABI version {L.lbdrn_plane3_abi_version()}, this binding is for {ABI_VERSION}")
-        _lib = L
-    return _lib
-
-
-def available():
-    try:
-        lib()
-        return True
-    except (Plane3Error, OSError):
-        return False
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise Plane3Error(f"{what}: {(lib().lbdrn_plane3_last_error() or b'').decode(errors='replace')}", rc)
+_i32, _vp, _sz, _i32p = ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)
+SIGNATURES = {      # name -> (restype, argtypes): every function of include/lbdrn_plane3.h
+    "lbdrn_plane3_last_error": (ctypes.c_char_p, []),
+    "lbdrn_plane3_abi_version": (ctypes.c_int, []),
+    "lbdrn_plane3_bound": (_sz, [_i32, _i32, _i32]),
+    "lbdrn_plane3_encode_workspace": (_sz, [_i32, _i32, _i32]),
+    "lbdrn_plane3_decode_workspace": (_sz, [_i32, _i32, _i32]),
+    "lbdrn_plane3_encode": (ctypes.c_int, [_vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "lbdrn_plane3_info": (ctypes.c_int, [ctypes.c_char_p, _sz, _i32p, _i32p, _i32p, _i32p]),
+    "lbdrn_plane3_decode": (ctypes.c_int, [_vp, _sz, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+}
+_NATIVE = Library("liblbdrn_plane3.so", "LBDRN_PLANE3_LIB", "lbdrn_plane3_", ABI_VERSION, SIGNATURES, Plane3Error)
+lib, available, _check, _PATH = _NATIVE.lib, _NATIVE.available, _NATIVE.check, _NATIVE.path
 
 
 def info(body):

@@ -15,23 +15,17 @@ csrc/pyramid.hip, csrc/pyramid.inc).  Built by csrc/build.py beside liblbdrn_qua
         any TIFF this package reads -> a tiled, Deflate-compressed file with its overviews, read, reduced and written on the
         GPU; the georeferencing tags of IN are carried over."""
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PATH = os.environ.get("LBDRN_PYRAMID_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_pyramid.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library, NativeError  # noqa: F401
+
 ABI_VERSION = 1
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
 AVERAGE, NEAREST = 0, 1                                             # LBDRN_PYR_AVERAGE, LBDRN_PYR_NEAREST
 RESAMPLINGS = {"average": AVERAGE, "nearest": NEAREST}
 DEFAULT_TILE = 256                                                  # tiff_write.DEFAULT_TILE
 
-_lib = None
 
-
-class PyramidError(RuntimeError):
-    def __init__(self, message, status=None):
-        super().__init__(message)
-        self.status = status
+class PyramidError(NativeError):
+    pass
 
 
 class Desc(ctypes.Structure):
@@ -41,38 +35,18 @@ class Desc(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("row_pitch", ctypes.c_int64), ("plane_pitch", ctypes.c_int64)]
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_PATH):
-            raise PyramidError(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
-        L = ctypes.CDLL(_PATH)
-        i32, vp, sz = ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t
-        dp, ip = ctypes.POINTER(Desc), ctypes.POINTER(ctypes.c_int32)
-        L.lbdrn_pyr_last_error.restype = ctypes.c_char_p
-        L.lbdrn_pyr_abi_version.restype = ctypes.c_int
-        L.lbdrn_pyr_level_count.argtypes = [i32, i32, i32]
-        L.lbdrn_pyr_level_size.argtypes = [i32, i32, i32, ip, ip]
-        L.lbdrn_pyr_level_offset.argtypes, L.lbdrn_pyr_level_offset.restype = [dp, i32], sz
-        L.lbdrn_pyr_output_bytes.argtypes, L.lbdrn_pyr_output_bytes.restype = [dp, i32], sz
-        L.lbdrn_pyr_build.argtypes = [dp, vp, i32, vp, sz, vp]
-        if L.lbdrn_pyr_abi_version() != ABI_VERSION:
-            raise PyramidError(f"{_PATH}: ABI version {L.lbdrn_pyr_abi_version()}, this binding is for {ABI_VERSION}")
-        _lib = L
-    return _lib
-
-
-def available():
-    try:
-        lib()
-        return True
-    except (PyramidError, OSError):
-        return False
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise PyramidError(f"{what}: {(lib().lbdrn_pyr_last_error() or b'').decode(errors='replace')}", rc)
+_i32, _vp, _sz, _dp, _ip = ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Desc), ctypes.POINTER(ctypes.c_int32)
+SIGNATURES = {      # name -> (restype, argtypes): every function of include/lbdrn_pyramid.h
+    "lbdrn_pyr_last_error": (ctypes.c_char_p, []),
+    "lbdrn_pyr_abi_version": (ctypes.c_int, []),
+    "lbdrn_pyr_level_count": (ctypes.c_int, [_i32, _i32, _i32]),
+    "lbdrn_pyr_level_size": (ctypes.c_int, [_i32, _i32, _i32, _ip, _ip]),
+    "lbdrn_pyr_level_offset": (_sz, [_dp, _i32]),
+    "lbdrn_pyr_output_bytes": (_sz, [_dp, _i32]),
+    "lbdrn_pyr_build": (ctypes.c_int, [_dp, _vp, _i32, _vp, _sz, _vp]),
+}
+_NATIVE = Library("liblbdrn_pyramid.so", "LBDRN_PYRAMID_LIB", "lbdrn_pyr_", ABI_VERSION, SIGNATURES, PyramidError)
+lib, available, _check, _PATH = _NATIVE.lib, _NATIVE.available, _NATIVE.check, _NATIVE.path
 
 
 # ---------------------------------------------------------------- the levels of a raster (needs neither library nor device)

@@ -16,57 +16,33 @@ The default peak is 10000, the fixed PSNR peak of decode.py's `PSNR:` record."""
 import ctypes
 import json
 import math
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PATH = os.environ.get("LBDRN_QUALITY_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_quality.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library, NativeError  # noqa: F401
+
 ABI_VERSION = 1
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
 SSIM, SAM = 1, 2                                                    # LBDRN_QUALITY_SSIM, LBDRN_QUALITY_SAM
 HIST_BINS = 257
 BAND_WORDS, PIXEL_WORDS = 5 + HIST_BINS + 2, 4                      # 8-byte fields of a band record and of the pixel record
 DEFAULT_PEAK = 10000.0
 
-_lib = None
+
+class QualityError(NativeError):
+    pass
 
 
-class QualityError(RuntimeError):
-    def __init__(self, message, status=None):
-        super().__init__(message)
-        self.status = status
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_PATH):
-            raise QualityError(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
-        L = ctypes.CDLL(_PATH)
-        i32, i64, u32, vp, sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t
-        L.lbdrn_quality_last_error.restype = ctypes.c_char_p
-        L.lbdrn_quality_abi_version.restype = ctypes.c_int
-        L.lbdrn_quality_result_bytes.argtypes, L.lbdrn_quality_result_bytes.restype = [i32], sz
-        L.lbdrn_quality_workspace.argtypes, L.lbdrn_quality_workspace.restype = [i32, i32, i32, u32], sz
-        L.lbdrn_quality_compare.argtypes = [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, ctypes.c_double, u32, vp, vp, sz, vp]
-        if L.lbdrn_quality_abi_version() != ABI_VERSION:
-            raise QualityError(f"{_PATH}: ABI version {L.lbdrn_quality_abi_version()}, this binding is for {ABI_VERSION}")
-        _lib = L
-    return _lib
-
-
-def available():
-    try:
-        lib()
-        return True
-    except (QualityError, OSError):
-        return False
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise QualityError(f"{what}: {(lib().lbdrn_quality_last_error() or b'').decode(errors='replace')}", rc)
+_i32, _i64, _u32, _vp, _sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t
+SIGNATURES = {      # name -> (restype, argtypes): every function of include/lbdrn_quality.h
+    "lbdrn_quality_last_error": (ctypes.c_char_p, []),
+    "lbdrn_quality_abi_version": (ctypes.c_int, []),
+    "lbdrn_quality_result_bytes": (_sz, [_i32]),
+    "lbdrn_quality_workspace": (_sz, [_i32, _i32, _i32, _u32]),
+    "lbdrn_quality_compare": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, ctypes.c_double, _u32, _vp, _vp,
+                                             _sz, _vp]),
+}
+_NATIVE = Library("liblbdrn_quality.so", "LBDRN_QUALITY_LIB", "lbdrn_quality_", ABI_VERSION, SIGNATURES, QualityError)
+lib, available, _check, _PATH = _NATIVE.lib, _NATIVE.available, _NATIVE.check, _NATIVE.path
 
 
 # ---------------------------------------------------------------- the result and what is derived from it

@@ -2,59 +2,30 @@
 from the codec's own reconstruction, quantised for a stated maximum error and Rice-coded per row on the GPU
 (csrc/resid.hip, csrc/resid.inc).  Built by csrc/build.py beside liblbdrn_hip.so; LBDRN_RESID_LIB names another file."""
 import ctypes
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PATH = os.environ.get("LBDRN_RESID_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_resid.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library, NativeError  # noqa: F401
+
 ABI_VERSION = 1
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
 MAX_TAU = 65535
 
-_lib = None
+
+class ResidError(NativeError):
+    pass
 
 
-class ResidError(RuntimeError):
-    def __init__(self, message, status=None):
-        super().__init__(message)
-        self.status = status
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_PATH):
-            raise ResidError(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
-        L = ctypes.CDLL(_PATH)
-        i32, vp, sz = ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        L.lbdrn_resid_last_error.restype = ctypes.c_char_p
-        L.lbdrn_resid_abi_version.restype = ctypes.c_int
-        L.lbdrn_resid_bound.argtypes = [i32, i32, i32]
-        L.lbdrn_resid_bound.restype = sz
-        L.lbdrn_resid_workspace.argtypes = [i32, i32, i32]
-        L.lbdrn_resid_workspace.restype = sz
-        L.lbdrn_resid_decode_workspace.argtypes = [i32, i32, i32]
-        L.lbdrn_resid_decode_workspace.restype = sz
-        L.lbdrn_resid_encode.argtypes = [vp, vp, i32, i32, i32, i32, vp, sz, vp, vp, sz, vp]
-        L.lbdrn_resid_info.argtypes = [ctypes.c_char_p, sz, i32p, i32p, i32p, i32p]
-        L.lbdrn_resid_decode.argtypes = [vp, sz, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-        if L.lbdrn_resid_abi_version() != ABI_VERSION:
-            raise ResidError(f"{_PATH}: ABI version {L.lbdrn_resid_abi_version()}, this binding is for {ABI_VERSION}")
-        _lib = L
-    return _lib
-
-
-def available():
-    try:
-        lib()
-        return True
-    except (ResidError, OSError):
-        return False
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise ResidError(f"{what}: {(lib().lbdrn_resid_last_error() or b'').decode(errors='replace')}", rc)
+_i32, _vp, _sz, _i32p = ctypes.c_int32, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int32)
+SIGNATURES = {      # name -> (restype, argtypes): every function of include/lbdrn_resid.h
+    "lbdrn_resid_last_error": (ctypes.c_char_p, []),
+    "lbdrn_resid_abi_version": (ctypes.c_int, []),
+    "lbdrn_resid_bound": (_sz, [_i32, _i32, _i32]),
+    "lbdrn_resid_workspace": (_sz, [_i32, _i32, _i32]),
+    "lbdrn_resid_decode_workspace": (_sz, [_i32, _i32, _i32]),
+    "lbdrn_resid_encode": (ctypes.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "lbdrn_resid_info": (ctypes.c_int, [ctypes.c_char_p, _sz, _i32p, _i32p, _i32p, _i32p]),
+    "lbdrn_resid_decode": (ctypes.c_int, [_vp, _sz, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+}
+_NATIVE = Library("liblbdrn_resid.so", "LBDRN_RESID_LIB", "lbdrn_resid_", ABI_VERSION, SIGNATURES, ResidError)
+lib, available, _check, _PATH = _NATIVE.lib, _NATIVE.available, _NATIVE.check, _NATIVE.path
 
 
 def info(body):

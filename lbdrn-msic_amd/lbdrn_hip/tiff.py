@@ -12,27 +12,21 @@ csrc/tiff.hip, csrc/tiff.inc).  Built by csrc/build.py beside liblbdrn_hip.so; L
 Everything outside the subset raises ValueError naming the tag and value before any device work.  Georeferencing tags are
 never interpreted: read_geo_tags copies them for a writer to carry over."""
 import ctypes
-import os
 import struct
 import zlib
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PATH = os.environ.get("LBDRN_TIFF_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_tiff.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library, NativeError  # noqa: F401
+
 ABI_VERSION = 1
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
 COMP_NONE, COMP_LZW, COMP_DEFLATE, COMP_DEFLATE_OLD, COMP_PACKBITS = 1, 5, 8, 32946, 32773
 STATUS_TEXT = {1: "the stream ends before the segment is complete", 2: "invalid code", 3: "a match distance points before the segment",
                4: "bad zlib header", 5: "wrong Adler-32"}
 
-_lib = None
 
-
-class TiffError(RuntimeError):
-    def __init__(self, message, status=None):
-        super().__init__(message)
-        self.status = status
+class TiffError(NativeError):
+    pass
 
 
 class Layout(ctypes.Structure):
@@ -41,40 +35,17 @@ class Layout(ctypes.Structure):
                                               "compression", "predictor")]
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_PATH):
-            raise TiffError(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
-        L = ctypes.CDLL(_PATH)
-        vp, sz = ctypes.c_void_p, ctypes.c_size_t
-        lp = ctypes.POINTER(Layout)
-        L.lbdrn_tiff_last_error.restype = ctypes.c_char_p
-        L.lbdrn_tiff_abi_version.restype = ctypes.c_int
-        L.lbdrn_tiff_segment_count.argtypes = [lp]
-        L.lbdrn_tiff_segment_count.restype = sz
-        L.lbdrn_tiff_segment_cap.argtypes = [ctypes.c_int32]
-        L.lbdrn_tiff_segment_cap.restype = sz
-        L.lbdrn_tiff_workspace.argtypes = [lp]
-        L.lbdrn_tiff_workspace.restype = sz
-        L.lbdrn_tiff_decode.argtypes = [lp, vp, sz, vp, vp, sz, vp, vp, vp, sz, vp]
-        if L.lbdrn_tiff_abi_version() != ABI_VERSION:
-            raise TiffError(f"{_PATH}: ABI version {L.lbdrn_tiff_abi_version()}, this binding is for {ABI_VERSION}")
-        _lib = L
-    return _lib
-
-
-def available():
-    try:
-        lib()
-        return True
-    except (TiffError, OSError):
-        return False
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise TiffError(f"{what}: {(lib().lbdrn_tiff_last_error() or b'').decode(errors='replace')}", rc)
+_vp, _sz, _lp = ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Layout)
+SIGNATURES = {      # name -> (restype, argtypes): every function of include/lbdrn_tiff.h
+    "lbdrn_tiff_last_error": (ctypes.c_char_p, []),
+    "lbdrn_tiff_abi_version": (ctypes.c_int, []),
+    "lbdrn_tiff_segment_count": (_sz, [_lp]),
+    "lbdrn_tiff_segment_cap": (_sz, [ctypes.c_int32]),
+    "lbdrn_tiff_workspace": (_sz, [_lp]),
+    "lbdrn_tiff_decode": (ctypes.c_int, [_lp, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+}
+_NATIVE = Library("liblbdrn_tiff.so", "LBDRN_TIFF_LIB", "lbdrn_tiff_", ABI_VERSION, SIGNATURES, TiffError)
+lib, available, _check, _PATH = _NATIVE.lib, _NATIVE.available, _NATIVE.check, _NATIVE.path
 
 
 # ---------------------------------------------------------------- the parser

@@ -19,25 +19,19 @@ three or more 8-bit bands are tagged RGB, the rest extra samples, as GDAL's GTif
 
 With neither overviews nor geo a file is byte for byte what it was before these options existed."""
 import ctypes
-import os
 import struct
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_PATH = os.environ.get("LBDRN_TIFFW_LIB") or os.path.join(os.path.dirname(_HERE), "liblbdrn_tiffw.so")
+from ._native import E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE, Library, NativeError  # noqa: F401
+
 ABI_VERSION = 1
-E_ARG, E_DEVICE, E_UNSUPPORTED, E_WORKSPACE = -1, -2, -3, -4      # lbdrn_status of include/lbdrn_hip.h
 COMP_NONE, COMP_DEFLATE = 1, 8
 DEFAULT_TILE = 256
 
-_lib = None
 
-
-class TiffWriteError(RuntimeError):
-    def __init__(self, message, status=None):
-        super().__init__(message)
-        self.status = status
+class TiffWriteError(NativeError):
+    pass
 
 
 class Layout(ctypes.Structure):
@@ -46,38 +40,20 @@ class Layout(ctypes.Structure):
                                               "compression", "predictor")]
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_PATH):
-            raise TiffWriteError(f"{_PATH} not built (python lbdrn-msic_amd/csrc/build.py)")
-        L = ctypes.CDLL(_PATH)
-        vp, sz = ctypes.c_void_p, ctypes.c_size_t
-        lp = ctypes.POINTER(Layout)
-        L.lbdrn_tiffw_last_error.restype = ctypes.c_char_p
-        L.lbdrn_tiffw_abi_version.restype = ctypes.c_int
-        for name, args in (("segment_count", [lp]), ("segment_cap", [ctypes.c_int32]), ("bound", [sz]), ("block_tokens", []),
-                           ("output_bytes", [lp]), ("workspace", [lp])):
-            f = getattr(L, "lbdrn_tiffw_" + name)
-            f.argtypes, f.restype = args, sz
-        L.lbdrn_tiffw_encode.argtypes = [lp, vp, vp, sz, vp, vp, vp, vp, sz, vp]
-        if L.lbdrn_tiffw_abi_version() != ABI_VERSION:
-            raise TiffWriteError(f"{_PATH}: ABI version {L.lbdrn_tiffw_abi_version()}, this binding is for {ABI_VERSION}")
-        _lib = L
-    return _lib
-
-
-def available():
-    try:
-        lib()
-        return True
-    except (TiffWriteError, OSError):
-        return False
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise TiffWriteError(f"{what}: {(lib().lbdrn_tiffw_last_error() or b'').decode(errors='replace')}", rc)
+_vp, _sz, _lp = ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(Layout)
+SIGNATURES = {      # name -> (restype, argtypes): every function of include/lbdrn_tiff_write.h
+    "lbdrn_tiffw_last_error": (ctypes.c_char_p, []),
+    "lbdrn_tiffw_abi_version": (ctypes.c_int, []),
+    "lbdrn_tiffw_segment_count": (_sz, [_lp]),
+    "lbdrn_tiffw_segment_cap": (_sz, [ctypes.c_int32]),
+    "lbdrn_tiffw_bound": (_sz, [_sz]),
+    "lbdrn_tiffw_block_tokens": (_sz, []),
+    "lbdrn_tiffw_output_bytes": (_sz, [_lp]),
+    "lbdrn_tiffw_workspace": (_sz, [_lp]),
+    "lbdrn_tiffw_encode": (ctypes.c_int, [_lp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp]),
+}
+_NATIVE = Library("liblbdrn_tiffw.so", "LBDRN_TIFFW_LIB", "lbdrn_tiffw_", ABI_VERSION, SIGNATURES, TiffWriteError)
+lib, available, _check, _PATH = _NATIVE.lib, _NATIVE.available, _NATIVE.check, _NATIVE.path
 
 
 # ---------------------------------------------------------------- the layout of a call
