@@ -54,12 +54,17 @@ typedef struct lbdrn_geom {
     int32_t C, H, W;      /* bands, rows, columns */
     int32_t K;            /* low bits dropped (encode.py:178) */
     int32_t D;            /* neighbourhood radius, window (2D+1)^2 (encode.py:184) */
-    int32_t msb_max;      /* MSB.max(): LBDRNdataset.py:120, decode.py:93 */
+    int32_t msb_max;      /* MSB.max(): LBDRNdataset.py:120, decode.py:93.  It divides every colour feature.  0 -- an MSB plane
+                           * that is zero everywhere, every sample of the tile below 2^K -- is normalised by 1: every entry
+                           * point that takes a geometry reads max(msb_max, 1), so such a tile's colour features are exact
+                           * zeros (the reference divides 0 by 0 there and carries NaN through the fit and the decoder).
+                           * Nothing changes for msb_max >= 1. */
     int32_t use_colors;   /* constants.py:11 */
     int32_t relative;     /* constants.py:14 */
     int32_t P;            /* positional features per axis: 0, 1 or 1+2*N_FREQ (constants.py:3-8) */
     int32_t reserved;
-    const float *rowtab;  /* device [H][P]: ph-derived features (LBDRNdataset.py:108-118) */
+    const float *rowtab;  /* device [H][P]: ph-derived features (LBDRNdataset.py:108-118); an axis of ONE pixel has position 0
+                           * (features.pos_tables: the reference's 2 * 0 / (1 - 1) - 1 is NaN) */
     const float *coltab;  /* device [W][P]: pw-derived features */
 } lbdrn_geom;
 

@@ -138,7 +138,7 @@ int lbdrn_features(const lbdrn_geom* g, const uint16_t* msb, const int64_t* idx,
     LBDRN_REQUIRE(msb && features && n >= 0, "msb/features null or n negative");
     LBDRN_REQUIRE(idx || n <= (int64_t)g->H * g->W, "n exceeds the pixel count");
     NEED_DEVICE();
-    return generic_features(*g, msb, idx, n, 0, features, (hipStream_t)stream);
+    return generic_features(launch_geom(*g), msb, idx, n, 0, features, (hipStream_t)stream);
 }
 
 size_t lbdrn_forward_workspace(const lbdrn_net* net, int64_t B)
@@ -221,9 +221,10 @@ int lbdrn_decode_fused(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
     if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
+    const lbdrn_geom gl = launch_geom(*g);
     if (use_mfma)
-        return mfma_decode(*g, *net, msb, params, out, y_out, workspace, workspace_bytes, (hipStream_t)stream);
-    return generic_decode(*g, *net, msb, params, out, y_out, workspace, workspace_bytes, (hipStream_t)stream);
+        return mfma_decode(gl, *net, msb, params, out, y_out, workspace, workspace_bytes, (hipStream_t)stream);
+    return generic_decode(gl, *net, msb, params, out, y_out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* img, const uint16_t* msb,
@@ -241,10 +242,11 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
     if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
+    const lbdrn_geom gl = launch_geom(*g);
     if (use_mfma)
-        return mfma_eval_sse(*g, *net, img, msb, params, sse, workspace, workspace_bytes, background, fast, x16,
+        return mfma_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, background, fast, x16,
                              (hipStream_t)stream);
-    return generic_eval_sse(*g, *net, img, msb, params, sse, workspace, workspace_bytes, (hipStream_t)stream);
+    return generic_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t lbdrn_train_workspace(const lbdrn_geom* g, const lbdrn_net* net, int32_t batch_size)
@@ -272,7 +274,7 @@ int lbdrn_train_prepare(const lbdrn_geom* g, const lbdrn_net* net, const uint16_
     }
     if (int rc = workspace_fits("train", workspace, workspace_bytes, lbdrn_train_workspace(g, net, batch_size))) return rc;
     if (ok && path != LBDRN_PATH_GENERIC)
-        return mfma_train_prepare(*g, *net, img, msb, batch_size, workspace, workspace_bytes, (hipStream_t)stream);
+        return mfma_train_prepare(launch_geom(*g), *net, img, msb, batch_size, workspace, workspace_bytes, (hipStream_t)stream);
     return 0;
 }
 
@@ -297,10 +299,11 @@ int lbdrn_train_epoch(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t*
     }
     LBDRN_REQUIRE(path >= LBDRN_PATH_AUTO && path <= LBDRN_PATH_MFMA, "unknown path %d", path);
     if (int rc = workspace_fits("train", workspace, workspace_bytes, lbdrn_train_workspace(g, net, batch_size))) return rc;
+    const lbdrn_geom gl = launch_geom(*g);
     if (ok && path != LBDRN_PATH_GENERIC)
-        return mfma_train_epoch(*g, *net, img, msb, perm, n, batch_size, params, exp_avg, exp_avg_sq,
+        return mfma_train_epoch(gl, *net, img, msb, perm, n, batch_size, params, exp_avg, exp_avg_sq,
                                 adam_step0, lr, losses, workspace, workspace_bytes, (hipStream_t)stream, alone);
-    return generic_train_epoch(*g, *net, img, msb, perm, n, batch_size, params, exp_avg, exp_avg_sq,
+    return generic_train_epoch(gl, *net, img, msb, perm, n, batch_size, params, exp_avg, exp_avg_sq,
                                adam_step0, lr, losses, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -347,7 +350,7 @@ int lbdrn_train_epoch_group(int32_t count, const lbdrn_geom* const* g, const lbd
     // side by side on the fused step where the shape has one; otherwise (and for any shape the group launch does not
     // take) one after another: same numbers either way
     if (count > 1 && path != LBDRN_PATH_GENERIC && mfma_train_supported(*g[0], *net, batch_size)) {
-        const int rc = mfma_train_epoch_group(count, *g[0], *net, perm, n, batch_size, params, exp_avg, exp_avg_sq,
+        const int rc = mfma_train_epoch_group(count, launch_geom(*g[0]), *net, perm, n, batch_size, params, exp_avg, exp_avg_sq,
                                               adam_step0, lr, losses, workspace, workspace_bytes, (hipStream_t)stream, false);
         if (rc != LBDRN_E_UNSUPPORTED) return rc;
     }

@@ -53,6 +53,15 @@ inline int feature_dim(const lbdrn_geom& g)
     return 2 * g.P + (g.use_colors ? g.C * side * side : 0);
 }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// The geometry the launches of an entry point read: the caller's, with the divisor of the normalisation at least 1.  An
+// MSB plane that is zero everywhere (msb_max == 0: every sample below 2^K) would make every colour feature 0 / 0; it is
+// normalised by 1, so its features are exact zeros (lbdrn_hip.h, at msb_max).  Nothing changes for msb_max >= 1.
+inline lbdrn_geom launch_geom(const lbdrn_geom& g)
+{
+    lbdrn_geom r = g;
+    if (r.msb_max < 1) r.msb_max = 1;
+    return r;
+}
 
 // the dynamic-LDS ceiling of a kernel is told to the runtime once per device and kernel (a cache of an idempotent
 // setting; several host threads may get here together)

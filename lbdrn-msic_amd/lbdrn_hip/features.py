@@ -50,6 +50,8 @@ class FeatCfg:
 def _axis_table(n, cfg):
     with np.errstate(all="ignore"):
         pos = (2 * np.arange(n) / (n - 1) - 1).astype(np.float32)   # float64 ramp, stored as f32
+        if n == 1:
+            pos = np.zeros(1, np.float32)   # 2*0/0 - 1 is NaN in the reference: a single-pixel axis has position 0
         if not cfg.embedding:
             return np.ascontiguousarray(pos[:, None])
         freqs = cfg.sigma ** np.arange(cfg.n_freq) * np.pi           # float64

@@ -148,7 +148,8 @@ static void feat_row(const orc_feat_cfg *g, const uint16_t *msb, int y, int x, f
 {
     const int side = 2 * g->D + 1;
     const int64_t HW = (int64_t)g->H * g->W;
-    const float mx = (float)g->msb_max;
+    /* an MSB plane that is zero everywhere is normalised by 1 (the reference divides 0 by 0 there): features 0.0f */
+    const float mx = (float)(g->msb_max < 1 ? 1 : g->msb_max);
     int o = 0;
     for (int p = 0; p < g->P; ++p) out[o++] = g->rowtab[(int64_t)y * g->P + p];
     for (int p = 0; p < g->P; ++p) out[o++] = g->coltab[(int64_t)x * g->P + p];

@@ -81,6 +81,8 @@ def pos_tables(H, W, cfg):
 
     def axis(n):
         pos = (2 * np.arange(n) / (n - 1) - 1).astype(np.float32)  # :110-112 (f64 then cast)
+        if n == 1:
+            pos = np.zeros(1, np.float32)  # the reference's 0 / 0: a single-pixel axis has position 0
         if not cfg.embedding:
             return pos[:, None].astype(np.float32)
         freq = cfg.sigma ** np.arange(cfg.n_freq) * np.pi  # f64, :114-115

@@ -324,7 +324,8 @@ def table_text():
 # ---------------------------------------------------------------------------------------------------------------------
 # the inputs of a row (shared by the CPU check of the ReLU kink condition and the GPU test)
 
-H, W, K = 13, 11, 5          # 143 pixels, H, W > D
+H, W, K = 13, 11, 5          # 143 pixels, H, W > D (the other half of the domain -- H <= D or W <= D, N < 64 -- is stepped by
+                             # tests/test_gpu_thin_rasters.py on the rows of tests/thin_cases.py)
 BS = 100                     # minibatches of 100 rows (two workgroups, the second part-filled) and of 43 (less than one)
 BS_TAIL = 71                 # 71, 71, 1: a one-row tail
 KINK = 1e-5                  # ReLU: no hidden pre-activation of the float64 reference within this of 0, relative to the layer's largest
