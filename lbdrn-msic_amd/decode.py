@@ -174,8 +174,8 @@ def decode_window_main(args, rank, world):
         logger.log.info(f"Recon: {recon_path}")
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
         if args.org_path is not None:
-            org_img = raster_io.read_raster(args.org_path)
-            org_img = org_img.reshape((-1,) + org_img.shape[-2:])[:, y0:y0 + h, x0:x0 + w]
+            org_img = raster_io.read_raster(args.org_path, window=(x0, y0, w, h))      # the window of the original alone
+            org_img = org_img.reshape((-1,) + org_img.shape[-2:])
             log_comparison(org_img, image, layer, args)    # (no bpsp: a property of the whole file)
     if world > 1:
         shard.finish()
@@ -190,6 +190,8 @@ def main(argv=None, shard_tiles=None):
     p.add_argument("-org", "--org_path", type=str, default=None, help="org path")
     p.add_argument("--window", type=int, nargs=4, default=None, metavar=("X0", "Y0", "W", "H"),
                    help="reconstruct this part of the scene only (scene pixels)")
+    p.add_argument("--org-window", dest="org_window", type=int, nargs=4, default=None, metavar=("X0", "Y0", "W", "H"),
+                   help="with -org: the file was encoded from this part of the original (encode.py --window)")
     p.add_argument("-o", "--out_path", type=str, default=None,
                    help="with --window: where the raster goes (default <name>_recon_x{X0}_y{Y0}_w{W}_h{H}.tif)")
     p.add_argument("--no-enhancement", dest="no_enhancement", action="store_true",
@@ -220,6 +222,8 @@ def main(argv=None, shard_tiles=None):
         p.error("--metrics-peak and --metrics-json go with --metrics")
     if args.metrics_peak is not None and not (args.metrics_peak > 0 and np.isfinite(args.metrics_peak)):
         p.error(f"--metrics-peak {args.metrics_peak}: a positive finite number")
+    if args.org_window is not None and (args.org_path is None or args.window is not None):
+        p.error("--org-window goes with -org and a whole decode")
     if args.out_tile is not None and args.out_compress is None:
         p.error("--out-tile goes with --out-compress")
     if args.out_tile is not None and (args.out_tile < 16 or args.out_tile % 16):
@@ -307,7 +311,8 @@ def main(argv=None, shard_tiles=None):
     if rank == 0:
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
         if args.org_path is not None:
-            org_img = raster_io.read_raster(args.org_path)
+            org_img = (raster_io.read_raster(args.org_path) if args.org_window is None else
+                       raster_io.read_raster(args.org_path, window=args.org_window))
             rec_img = raster_io.read_raster(recon_path)
             nbytes = os.path.getsize(args.bin_path)
             log_comparison(org_img, rec_img, layer, args)

@@ -35,6 +35,12 @@ IN_FLIGHT = int(os.environ["LBDRN_IN_FLIGHT"]) if "LBDRN_IN_FLIGHT" in os.enviro
 # progressing at a time on a GPU (None: codec.fit_many's default, 4)
 
 
+def tile_reads_wanted():
+    """LBDRN_TILE_READS=1: at -sr > 1 read each tile as a window of the scene (raster_io.read_raster(window=)), the next
+    one on a host thread, and never hold the scene; off by default.  Looked up when a run starts."""
+    return os.environ.get("LBDRN_TILE_READS", "") not in ("", "0")
+
+
 def write_image_header(header_path, split_ratio, width, height, K, bc, nl, D, nn_bytes_list,
                        base_bytes_list):
     data = container.pack_header(split_ratio, width, height, K, bc, nl, D, nn_bytes_list, base_bytes_list)
@@ -179,10 +185,53 @@ def build_parser():
     p.add_argument("-e", "--epochs", type=int, default=10, help="number of epochs to train (default: 10)")
     p.add_argument("-vd", "--val_duration", type=int, default=1,
                    help="number of epoch duration for val (default: 1)")
+    p.add_argument("--window", type=int, nargs=4, default=argparse.SUPPRESS, metavar=("X0", "Y0", "W", "H"),
+                   help="encode this part of the scene only (scene pixels); the output is named <name>_x{X0}_y{Y0}_w{W}_h{H}")
     p.add_argument("--max-error", dest="max_error", type=int, default=None, metavar="T",
                    help="append a residual layer that bounds |original - reconstruction| by T on every sample (0: lossless); "
                         "default: no layer")
     return p
+
+
+def scene_name(args):
+    """the stem of everything main() writes: the input's, with --window the window behind it"""
+    name = os.path.splitext(os.path.basename(args.path))[0]
+    win = getattr(args, "window", None)
+    return name if win is None else name + "_x{}_y{}_w{}_h{}".format(*win)
+
+
+def check_scene_window(parser, args):
+    """--window against the scene's size, before anything is read or written (codec.check_window's wording)"""
+    if getattr(args, "window", None) is not None:
+        try:
+            C, H, W, _ = raster_io.raster_shape(args.path)
+            args.window = list(codec.check_window(args.window, W, H))
+        except ValueError as e:
+            parser.error(f"--window: {e}")
+
+
+def scene_geometry(path, window):
+    """(C, height, width) of the scene to encode -- of the window where one is given -- without reading a pixel"""
+    C, H, W, _ = raster_io.raster_shape(path)
+    return (C, H, W) if window is None else (C, window[3], window[2])
+
+
+def tiles_ahead(path, window, wins):
+    """LBDRN_TILE_READS: the tiles `wins` (tile_windows entries) of the scene, or of its window, each read as a window of the
+    file; tile k + 1 is read on a host thread while the caller prepares tile k.  Yields [C,h,w] arrays in order."""
+    from concurrent.futures import ThreadPoolExecutor
+    ox, oy = (0, 0) if window is None else window[:2]
+
+    def read(win):
+        _, _, x0, y0, w, h = win
+        a = raster_io.read_raster(path, window=(ox + x0, oy + y0, w, h))
+        return np.ascontiguousarray(a.reshape((-1,) + a.shape[-2:]))
+    with ThreadPoolExecutor(1, thread_name_prefix="lbdrn-tile-read") as pool:
+        nxt = pool.submit(read, wins[0]) if wins else None
+        for k in range(len(wins)):
+            cur = nxt.result()
+            nxt = pool.submit(read, wins[k + 1]) if k + 1 < len(wins) else None
+            yield cur
 
 
 def main(argv=None, shard_tiles=None):
@@ -202,6 +251,8 @@ def main(argv=None, shard_tiles=None):
         container.check_base_codec(BASE_CODEC)
     except ValueError as e:
         parser.error(str(e))
+    check_scene_window(parser, args)
+    window = getattr(args, "window", None)
     rank, world = 0, 1
     if shard_tiles is None:
         shard_tiles = shard.env_world()[1] > 1
@@ -213,7 +264,7 @@ def main(argv=None, shard_tiles=None):
         np.random.seed(args.seed)
         random.seed(args.seed)
     org_path = args.path
-    filename = os.path.splitext(os.path.basename(org_path))[0]
+    filename = scene_name(args)
     args.output_dir = "{}/{}_r{}_K{}_bc{}_nl{}_D{}_prec{}_lr{}_bs{}_e{}".format(
         args.output_dir, filename, args.split_ratio, args.K, args.base_channel, args.num_layers,
         args.D, args.precision, args.lr, args.batch_size, args.epochs)
@@ -237,23 +288,28 @@ def main(argv=None, shard_tiles=None):
     else:
         logger.create_logger(args.output_dir, "", log_file_only=True)
     start_time = time.time()
-    img = raster_io.read_raster(org_path)
-    img = img.reshape((-1,) + img.shape[-2:])
-    height, width = img.shape[-2:]
+    tile_reads = tile_reads_wanted() and args.split_ratio > 1
+    if tile_reads:
+        img = None
+        C, height, width = scene_geometry(org_path, window)
+    else:
+        img = raster_io.read_raster(org_path) if window is None else raster_io.read_raster(org_path, window=window)
+        img = img.reshape((-1,) + img.shape[-2:])
+        C, height, width = img.shape
     windows = list(tile_windows(width, height, args.split_ratio)) if args.split_ratio > 1 else [None]
-    n_feature = FeatCfg.from_constants().feature_dim(img.shape[0], args.D)
+    n_feature = FeatCfg.from_constants().feature_dim(C, args.D)
     # every tile's random draws, in tile order, whoever fits it: the reference runs the tiles one after
     # another on one generator (ref encode.py:231-262)
-    C = img.shape[0]
     draws = [codec.draw_fit(n_feature, args.base_channel, C, args.num_layers, args.epochs, args.val_duration)
              for _ in windows]
     mine, jobs = [t for t in range(len(windows)) if t % world == rank], []
+    ahead_tiles = tiles_ahead(org_path, window, [windows[t] for t in mine]) if tile_reads else None
     for t in mine:
         path, tile = org_path, img
         if windows[t] is not None:
             i, j, x0, y0, w, h = windows[t]
             path = f"{args.output_dir}/tile_{i}_{j}.tif"
-            tile = np.ascontiguousarray(img[:, y0:y0 + h, x0:x0 + w])
+            tile = next(ahead_tiles) if tile_reads else np.ascontiguousarray(img[:, y0:y0 + h, x0:x0 + w])
         jobs.append((path, tile))
     # the reference's MSB format is host work that needs nothing from the fit: it starts now (LBDRN_JP2_AHEAD=0: afterwards, as before)
     ahead = None
@@ -300,7 +356,7 @@ def main(argv=None, shard_tiles=None):
 
 def output_folder(args):
     """The directory main() writes a point into (ref encode.py:207-209)."""
-    filename = os.path.splitext(os.path.basename(args.path))[0]
+    filename = scene_name(args)
     return "{}/{}_r{}_K{}_bc{}_nl{}_D{}_prec{}_lr{}_bs{}_e{}".format(
         args.output_dir, filename, args.split_ratio, args.K, args.base_channel, args.num_layers,
         args.D, args.precision, args.lr, args.batch_size, args.epochs)
@@ -330,12 +386,14 @@ def main_k_points(argv, Ks):
         container.check_base_codec(BASE_CODEC)
     except ValueError as e:
         parser.error(str(e))
+    check_scene_window(parser, base)
+    window = getattr(base, "window", None)
     if not base.randomness:
         torch.manual_seed(base.seed)
         np.random.seed(base.seed)
         random.seed(base.seed)
     org_path = base.path
-    filename = os.path.splitext(os.path.basename(org_path))[0]
+    filename = scene_name(base)
     outcome, point, todo = {}, {}, []
     for K in Ks:
         a = argparse.Namespace(**vars(base))
@@ -357,21 +415,26 @@ def main_k_points(argv, Ks):
         return outcome
     start_time = time.time()
     try:
-        img = raster_io.read_raster(org_path)
-        img = img.reshape((-1,) + img.shape[-2:])
-        height, width = img.shape[-2:]
+        tile_reads = tile_reads_wanted() and base.split_ratio > 1
+        if tile_reads:
+            img = None
+            C, height, width = scene_geometry(org_path, window)
+        else:
+            img = raster_io.read_raster(org_path) if window is None else raster_io.read_raster(org_path, window=window)
+            img = img.reshape((-1,) + img.shape[-2:])
+            C, height, width = img.shape
         windows = list(tile_windows(width, height, base.split_ratio)) if base.split_ratio > 1 else [None]
-        C = img.shape[0]
         n_feature = FeatCfg.from_constants().feature_dim(C, base.D)
         # one draw per tile, in tile order, serves every K (read-only: codec.fit_group)
         draws = [codec.draw_fit(n_feature, base.base_channel, C, base.num_layers, base.epochs, base.val_duration)
                  for _ in windows]
         tiles = []
+        ahead_tiles = tiles_ahead(org_path, window, windows) if tile_reads else None
         for win in windows:
             tile = img
             if win is not None:
                 i, j, x0, y0, w, h = win
-                tile = np.ascontiguousarray(img[:, y0:y0 + h, x0:x0 + w])
+                tile = next(ahead_tiles) if tile_reads else np.ascontiguousarray(img[:, y0:y0 + h, x0:x0 + w])
             tiles.append(tile)
         ahead = {}
         if BASE_CODEC.lower() in ("jp2", "jpeg2000", "jp2openjpeg") and os.environ.get("LBDRN_JP2_AHEAD", "1") != "0":

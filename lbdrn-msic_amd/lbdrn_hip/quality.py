@@ -230,14 +230,16 @@ def main(argv=None):
     p.add_argument("--json", type=str, default=None, metavar="FILE", help="write every figure, histograms included")
     args = p.parse_args(argv)
     from . import raster_io
-    ta, tb = raster_io.read_raster_device(args.a), raster_io.read_raster_device(args.b)
-    if args.window is not None:
+    if args.window is not None:      # checked against both rasters' sizes before a pixel is read, then only the windows are
         x0, y0, w, h = args.window
-        for t, name in ((ta, args.a), (tb, args.b)):
-            if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > t.shape[2] or y0 + h > t.shape[1]:
-                print(f"--window {x0} {y0} {w} {h} is not inside {name} ({t.shape[2]} x {t.shape[1]})", file=sys.stderr)
+        for name in (args.a, args.b):
+            _, H, W, _ = raster_io.raster_shape(name)
+            if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+                print(f"--window {x0} {y0} {w} {h} is not inside {name} ({W} x {H})", file=sys.stderr)
                 return 2
-        ta, tb = ta[:, y0:y0 + h, x0:x0 + w], tb[:, y0:y0 + h, x0:x0 + w]
+        ta, tb = (raster_io.read_raster_device(name, window=(x0, y0, w, h)) for name in (args.a, args.b))
+    else:
+        ta, tb = raster_io.read_raster_device(args.a), raster_io.read_raster_device(args.b)
     try:
         q = compare(ta, tb, peak=args.peak)
     except ValueError as e:

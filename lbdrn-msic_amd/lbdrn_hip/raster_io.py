@@ -9,6 +9,9 @@ gdal's ReadAsArray() returns them.  write_raster with a compression or tiling op
 go to lbdrn_hip.tiff_write, which builds and Deflate-compresses the segments on the GPU -- with overviews= the overview
 levels too, reduced on the GPU by lbdrn_hip.pyramid, and with geo= the georeferencing tags read_geo_tags copied from
 another file.  read_raster(path, overview=k) reads level k of such a file.
+read_raster(path, window=(x0, y0, w, h)) and read_raster_device(..., window=) read that part alone, equal to the same slice of the
+whole read, from a read-only memory map: only the strips or tiles the window touches are read, uploaded and decoded
+(lbdrn_hip.tiff.plan_window); raster_shape(path) tells (C, H, W, dtype) from the tags.
 """
 import struct
 
@@ -43,9 +46,12 @@ def _check_overview(path, overview):
     return int(overview)
 
 
-def read_raster(path, overview=0):
+def read_raster(path, overview=0, window=None):
     """overview=k >= 1: level k of a pyramidal TIFF, through this package's parser and the GPU reader even where GDAL
-    imports; IndexError where the file has fewer levels."""
+    imports; IndexError where the file has fewer levels.  window=(x0, y0, w, h): that part of the raster (of level k) alone,
+    equal to the same slice of the whole read, without reading or decoding the rest of the file (_read_window)."""
+    if window is not None:
+        return _read_window(path, _check_overview(path, overview), window, None)
     if _check_overview(path, overview):
         from . import tiff
         with open(path, "rb") as f:
@@ -59,11 +65,13 @@ def read_raster(path, overview=0):
     return _read_tiff(path)
 
 
-def read_raster_device(path, device="cuda:0", overview=0):
+def read_raster_device(path, device="cuda:0", overview=0, window=None):
     """The raster as a contiguous [C,H,W] tensor on `device`, for callers that want the planes left in HBM: 16-bit samples as
     int16 storage, like every plane of this package.  A tiled or compressed TIFF never passes through host arrays.
-    overview=k >= 1: level k of a pyramidal TIFF, as read_raster has it."""
+    overview=k >= 1: level k of a pyramidal TIFF, as read_raster has it; window=(x0, y0, w, h): that part alone, [C,h,w]."""
     import torch
+    if window is not None:
+        return _read_window(path, _check_overview(path, overview), window, device)
     if _check_overview(path, overview):
         from . import tiff
         with open(path, "rb") as f:
@@ -84,6 +92,118 @@ def read_raster_device(path, device="cuda:0", overview=0):
             a = _read_tiff(path)
         else:
             return tiff.read_device_bytes(buf, path, device)
+    a = np.ascontiguousarray(a if a.ndim == 3 else a[None])
+    return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)
+
+
+def _classic_plain(buf):
+    """(tags, byte order, dtype, C, H, W, planar) of a file _read_tiff reads by itself -- a classic TIFF of uncompressed
+    strips -- or None.  Reads the header, the IFD and the tag arrays through slices: buf may be a memory map."""
+    bo = {b"II": "<", b"MM": ">"}.get(bytes(buf[:2]))
+    if bo is None or len(buf) < 8 or struct.unpack(bo + "H", buf[2:4])[0] != 42:
+        return None
+    off = struct.unpack(bo + "I", buf[4:8])[0]
+    n = struct.unpack(bo + "H", buf[off:off + 2])[0]
+    tags = {}
+    for i in range(n):
+        tag, typ, cnt, val = struct.unpack(bo + "HHI4s", buf[off + 2 + 12 * i:off + 14 + 12 * i])
+        size = {1: 1, 3: 2, 4: 4}.get(typ)
+        if size is None:
+            continue
+        at = struct.unpack(bo + "I", val)[0]
+        raw = val if size * cnt <= 4 else buf[at:at + size * cnt]
+        tags[tag] = list(struct.unpack(bo + f"{cnt}" + {1: "B", 3: "H", 4: "I"}[typ], raw[:size * cnt]))
+    if tags.get(259, [1])[0] != 1 or 322 in tags:
+        return None
+    bits = tags.get(258, [1])
+    if len(set(bits)) != 1:
+        raise ValueError("mixed bit depths")
+    dt = {(8, 1): "u1", (16, 1): "u2", (32, 1): "u4", (32, 3): "f4", (64, 3): "f8"}[(bits[0], tags.get(339, [1])[0])]
+    return tags, bo, np.dtype(bo + dt), tags.get(277, [1])[0], tags[257][0], tags[256][0], tags.get(284, [1])[0]
+
+
+def _window_of_strips(buf, plain, window):
+    """_read_tiff's array, windowed: _read_tiff joins the strips and reshapes, so row y of band b lies at a known place of
+    the joined stream; only the window's rows are taken from the file, then the columns are sliced"""
+    tags, bo, dt, C, H, W, planar = plain
+    x0, y0, w, h = window
+    offs, cnts = tags[273], tags[279]
+    starts = np.concatenate([[0], np.cumsum(cnts)])
+
+    def joined(a, b):      # bytes [a, b) of the strips one after another
+        out, k = [], int(np.searchsorted(starts, a, side="right")) - 1
+        while a < b and k < len(offs):
+            n = min(b, int(starts[k + 1])) - a
+            out.append(buf[offs[k] + a - int(starts[k]):offs[k] + a - int(starts[k]) + n])
+            a, k = a + n, k + 1
+        return b"".join(out)
+    if planar == 2:
+        row = W * dt.itemsize
+        a = np.stack([np.frombuffer(joined((b * H + y0) * row, (b * H + y0 + h) * row), dt).reshape(h, W) for b in range(C)])
+    else:
+        row = W * C * dt.itemsize
+        a = np.frombuffer(joined(y0 * row, (y0 + h) * row), dt).reshape(h, W, C).transpose(2, 0, 1)
+    a = np.ascontiguousarray(a[:, :, x0:x0 + w].astype(dt.newbyteorder("=")))
+    return a[0] if C == 1 else a
+
+
+def raster_shape(path, overview=0):
+    """(C, H, W, dtype) of what read_raster(path, overview) returns, C = 1 for an [H,W] result; no pixel data is read"""
+    overview = _check_overview(path, overview)
+    if path.endswith(".npy"):
+        a = np.load(path, mmap_mode="r")
+        return ((1,) if a.ndim == 2 else ()) + tuple(a.shape) + (a.dtype,)
+    g = _gdal()
+    if g is not None and not overview:
+        from osgeo import gdal_array
+        ds = g.Open(path)
+        return (ds.RasterCount, ds.RasterYSize, ds.RasterXSize,
+                np.dtype(gdal_array.GDALTypeCodeToNumericTypeCode(ds.GetRasterBand(1).DataType)))
+    from . import tiff
+    buf = tiff.open_map(path)
+    try:
+        plain = None if overview else _classic_plain(buf)
+        if plain is not None:
+            return plain[3], plain[4], plain[5], plain[2].newbyteorder("=")
+        lay = tiff._parse(buf, path, _overview_ifd(buf, path, overview) if overview else 0, False).layout
+        return lay.C, lay.H, lay.W, np.dtype(np.uint8 if lay.bits == 8 else np.uint16)
+    finally:
+        if not isinstance(buf, bytes):
+            buf.close()
+
+
+def _read_window(path, overview, window, device):
+    """read_raster (device None) and read_raster_device with a window: the same slice of the whole read, same dtype, [h,w]
+    for one band where read_raster returns [H,W].  A .npy array is memory-mapped; GDAL reads the window where it imports and
+    the full resolution is asked for; everything else is read from a read-only memory map of the file, this module's own
+    uncompressed strips by their rows, the rest through tiff.read_window_bytes -- only the touched segments are uploaded."""
+    from .codec import check_window
+    a = None
+    if path.endswith(".npy"):
+        m = np.load(path, mmap_mode="r")
+        x0, y0, w, h = check_window(window, m.shape[-1], m.shape[-2])
+        a = np.array(m[..., y0:y0 + h, x0:x0 + w])
+    elif _gdal() is not None and not overview:
+        ds = _gdal().Open(path)
+        a = ds.ReadAsArray(*check_window(window, ds.RasterXSize, ds.RasterYSize))
+    else:
+        from . import tiff
+        buf = tiff.open_map(path)
+        try:
+            plain = None if overview else _classic_plain(buf)
+            if plain is not None:
+                a = _window_of_strips(buf, plain, check_window(window, plain[5], plain[4]))
+            elif device is not None:
+                return tiff.read_window_bytes(buf, path, window, device, _overview_ifd(buf, path, overview) if overview else 0)
+            else:
+                a = tiff._window(buf, path, window, None, _overview_ifd(buf, path, overview) if overview else 0, False)
+                a = a[0] if a.shape[0] == 1 else a
+        finally:
+            if not isinstance(buf, bytes):
+                buf.close()
+    if device is None:
+        return a
+    import torch
     a = np.ascontiguousarray(a if a.ndim == 3 else a[None])
     return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(device)
 

@@ -8,7 +8,12 @@ csrc/tiff.hip, csrc/tiff.inc).  Built by csrc/build.py beside liblbdrn_hip.so; L
     read_device(path, device)  contiguous [C,H,W] tensor in HBM: int16 storage for 16-bit samples, like every plane of this
                                package, uint8 for 8-bit ones
     read(path, device)         numpy, with the conventions of raster_io._read_tiff ([H,W] for one band)
+    plan_window(scene, window) the segments a window (x0, y0, w, h) touches, as a scene of their own: sub-layout, byte ranges of the
+                               file, the segment table rebased into the compact buffer of those ranges (host arithmetic)
+    read_window_bytes(buf, path, window, device, ifd)   that window as a [C,h,w] tensor: only the touched segments are read,
+                               uploaded and decoded; read_window(path, ...): the same over a read-only memory map -> numpy
 
+A file is read through len() and slices only: bytes, a memory map or anything else that has them.
 Everything outside the subset raises ValueError naming the tag and value before any device work.  Georeferencing tags are
 never interpreted: read_geo_tags copies them for a writer to carry over."""
 import ctypes
@@ -61,9 +66,10 @@ _WANTED = {254: "NewSubfileType", 256: "ImageWidth", 257: "ImageLength", 258: "B
 class Scene:
     """what parse() returns: the layout the library takes, the segment table, and the sample format for the host paths"""
 
-    def __init__(self, layout, offsets, counts, sample_format, byteorder):
+    def __init__(self, layout, offsets, counts, sample_format, byteorder, names=None):
         self.layout, self.offsets, self.counts = layout, offsets, counts
         self.sample_format, self.byteorder = sample_format, byteorder
+        self.names = names      # the sub-layout of a window: the file's own index of each segment, for the error messages
 
     @property
     def shape(self):
@@ -74,18 +80,24 @@ class Scene:
         return self.layout.compression == COMP_NONE and not self.layout.tiled
 
 
+def _unpack(fmt, buf, at):
+    """struct.unpack_from through a slice: the parser reads a file through len() and slices only, so that a memory map is
+    never copied whole and a wrapper that records its slices sees every byte that was touched"""
+    return struct.unpack(fmt, buf[at:at + struct.calcsize(fmt)])
+
+
 def _header(buf, path):
     """(byte order mark, BigTIFF?, offset of the first IFD)"""
     bo = {b"II": "<", b"MM": ">"}.get(bytes(buf[:2]))
     if bo is None or len(buf) < 8:
         raise ValueError(f"{path}: not a TIFF (no II / MM byte order mark)")
-    magic = struct.unpack_from(bo + "H", buf, 2)[0]
+    magic = _unpack(bo + "H", buf, 2)[0]
     if magic == 42:
-        return bo, False, struct.unpack_from(bo + "I", buf, 4)[0]
+        return bo, False, _unpack(bo + "I", buf, 4)[0]
     if magic == 43:
-        if len(buf) < 16 or struct.unpack_from(bo + "HH", buf, 4) != (8, 0):
+        if len(buf) < 16 or _unpack(bo + "HH", buf, 4) != (8, 0):
             raise ValueError(f"{path}: BigTIFF header with an offset size other than 8")
-        return bo, True, struct.unpack_from(bo + "Q", buf, 8)[0]
+        return bo, True, _unpack(bo + "Q", buf, 8)[0]
     raise ValueError(f"{path}: not a TIFF (magic {magic})")
 
 
@@ -105,13 +117,13 @@ def read_ifds(buf, path="TIFF"):
             raise ValueError(f"{path}: more than {MAX_IFDS} IFDs")
         if off + cnt_size > len(buf):
             raise ValueError(f"{path}: IFD {len(out)} (offset {off}) lies outside the file's {len(buf)} bytes")
-        n = struct.unpack_from(bo + cnt_fmt, buf, off)[0]
+        n = _unpack(bo + cnt_fmt, buf, off)[0]
         end = off + cnt_size + ent * n
         if end + nxt_size > len(buf):
             raise ValueError(f"{path}: IFD {len(out)} (offset {off}, {n} entries) lies outside the file's {len(buf)} bytes")
         seen.add(off)
         out.append(off)
-        off = struct.unpack_from(bo + nxt_fmt, buf, end)[0]
+        off = _unpack(bo + nxt_fmt, buf, end)[0]
     return out
 
 
@@ -133,14 +145,14 @@ def read_tags(buf, path="TIFF", ifd=0):
     cnt_fmt, cnt_size, ent, inline = ("Q", 8, 20, 8) if big else ("H", 2, 12, 4)
     if off + cnt_size > len(buf):
         raise ValueError(f"{path}: {name} lies outside the file")
-    n = struct.unpack_from(bo + cnt_fmt, buf, off)[0]
+    n = _unpack(bo + cnt_fmt, buf, off)[0]
     if off + cnt_size + ent * n > len(buf):
         raise ValueError(f"{path}: {name} lies outside the file")
     tags = {}
     for i in range(n):
         at = off + cnt_size + ent * i
-        tag, typ = struct.unpack_from(bo + "HH", buf, at)
-        cnt = struct.unpack_from(bo + ("Q" if big else "I"), buf, at + 4)[0]
+        tag, typ = _unpack(bo + "HH", buf, at)
+        cnt = _unpack(bo + ("Q" if big else "I"), buf, at + 4)[0]
         if tag not in _WANTED or typ not in _FIELD:
             continue
         code, size = _FIELD[typ]
@@ -148,17 +160,34 @@ def read_tags(buf, path="TIFF", ifd=0):
             raise ValueError(f"{path}: tag {tag} ({_WANTED[tag]}) has the non-integer type {typ}")
         val_at = at + 4 + (8 if big else 4)
         if size * cnt > inline:
-            val_at = struct.unpack_from(bo + ("Q" if big else "I"), buf, val_at)[0]
+            val_at = _unpack(bo + ("Q" if big else "I"), buf, val_at)[0]
         if val_at + size * cnt > len(buf):
             raise ValueError(f"{path}: the values of tag {tag} ({_WANTED[tag]}) lie outside the file")
-        tags[tag] = np.frombuffer(buf, np.dtype(bo + {"B": "u1", "b": "i1", "H": "u2", "h": "i2", "I": "u4", "i": "i4", "Q": "u8",
-                                                    "q": "i8"}[code]), cnt, val_at).astype(np.int64 if code in "bhiq" else np.uint64).tolist()
+        tags[tag] = np.frombuffer(buf[val_at:val_at + size * cnt], np.dtype(bo + {"B": "u1", "b": "i1", "H": "u2", "h": "i2", "I": "u4",
+                                                                                  "i": "i4", "Q": "u8", "q": "i8"}[code]),
+                                  cnt).astype(np.int64 if code in "bhiq" else np.uint64).tolist()
     return tags, bo, big
 
 
 def parse(buf, path="TIFF", ifd=0):
     """Scene of the first IFD, or of IFD number `ifd` of the chain (IndexError where the file has fewer); ValueError naming
     the tag and value for everything outside the subset."""
+    return _parse(buf, path, ifd, True)
+
+
+def _old_lzw(buf, path, offsets, counts, segments):
+    """ValueError for a segment of `segments` that is old-style LZW, as libtiff detects the old bit order"""
+    for i in segments:
+        o, c = int(offsets[i]), int(counts[i])
+        if c >= 2 and bytes(buf[o:o + 2]) in _OLD_LZW:
+            raise ValueError(f"{path}: Compression (259) = 5: segment {i} is old-style (LSB-first) LZW, which is not read here")
+
+
+_OLD_LZW = {bytes([0, b]) for b in range(1, 256, 2)}
+
+
+def _parse(buf, path, ifd, lzw_check):
+    """parse; lzw_check=False leaves the look at every LZW segment's first two bytes to the caller, who reads only some"""
     tags, bo, _ = read_tags(buf, path, ifd)
 
     def one(tag, default=None):
@@ -213,10 +242,8 @@ def parse(buf, path="TIFF", ifd=0):
     for i, (o, c) in enumerate(zip(offsets, counts)):
         if o + c > len(buf):
             raise ValueError(f"{path}: {names}: segment {i} (offset {o}, {c} bytes) lies outside the file's {len(buf)} bytes")
-    if comp == COMP_LZW:
-        for i, (o, c) in enumerate(zip(offsets, counts)):      # as libtiff detects the old bit order
-            if c >= 2 and buf[o] == 0 and (buf[o + 1] & 1):
-                raise ValueError(f"{path}: Compression (259) = 5: segment {i} is old-style (LSB-first) LZW, which is not read here")
+    if comp == COMP_LZW and lzw_check:
+        _old_lzw(buf, path, offsets, counts, range(nseg))
     lay = Layout(C, H, W, bits[0], 1 if bo == ">" else 0, planar, sw, sh, 1 if tiled else 0,
                  COMP_DEFLATE if comp == COMP_DEFLATE_OLD else comp, pred)
     return Scene(lay, np.asarray(offsets, np.uint64), np.asarray(counts, np.uint64), fmt[0], bo)
@@ -245,23 +272,23 @@ def read_geo_tags(buf, path="TIFF"):
     cnt_fmt, cnt_size, ent, inline = ("Q", 8, 20, 8) if big else ("H", 2, 12, 4)
     if off + cnt_size > len(buf):
         raise ValueError(f"{path}: {name} lies outside the file")
-    n = struct.unpack_from(bo + cnt_fmt, buf, off)[0]
+    n = _unpack(bo + cnt_fmt, buf, off)[0]
     if off + cnt_size + ent * n > len(buf):
         raise ValueError(f"{path}: {name} lies outside the file")
     out = []
     for i in range(n):
         at = off + cnt_size + ent * i
-        tag, typ = struct.unpack_from(bo + "HH", buf, at)
+        tag, typ = _unpack(bo + "HH", buf, at)
         if tag not in GEO_TAGS or typ != GEO_TAGS[tag][0]:
             continue
-        cnt = struct.unpack_from(bo + ("Q" if big else "I"), buf, at + 4)[0]
+        cnt = _unpack(bo + ("Q" if big else "I"), buf, at + 4)[0]
         size = GEO_TAGS[tag][1]
         val_at = at + 4 + (8 if big else 4)
         if size * cnt > inline:
-            val_at = struct.unpack_from(bo + ("Q" if big else "I"), buf, val_at)[0]
+            val_at = _unpack(bo + ("Q" if big else "I"), buf, val_at)[0]
         if val_at + size * cnt > len(buf):
             raise ValueError(f"{path}: the values of tag {tag} lie outside the file")
-        raw = np.frombuffer(buf, np.dtype(bo + "u%d" % size), cnt, val_at).astype("<u%d" % size).tobytes()
+        raw = np.frombuffer(buf[val_at:val_at + size * cnt], np.dtype(bo + "u%d" % size), cnt).astype("<u%d" % size).tobytes()
         out.append((int(tag), int(typ), int(cnt), raw))
     return out
 
@@ -275,6 +302,11 @@ def _segment_grid(lay):
         for ty in range(rows):
             for tx in range(per_row):
                 yield b, ty * lay.seg_h, tx * lay.seg_w
+
+
+def _name(scene, i):
+    """what an error calls segment i of the scene: its index in the file's own table"""
+    return i if scene.names is None else int(scene.names[i])
 
 
 def _read_host_deflate(buf, scene):
@@ -292,9 +324,9 @@ def _read_host_deflate(buf, scene):
         try:
             raw = zlib.decompress(bytes(buf[o:o + c]))
         except zlib.error as e:
-            raise TiffError(f"segment {i} is damaged: {e}") from None
+            raise TiffError(f"segment {_name(scene, i)} is damaged: {e}") from None
         if len(raw) < hh * lay.seg_w * spp * dt.itemsize:
-            raise TiffError(f"segment {i} is damaged: it holds {len(raw)} bytes of {hh * lay.seg_w * spp * dt.itemsize}")
+            raise TiffError(f"segment {_name(scene, i)} is damaged: it holds {len(raw)} bytes of {hh * lay.seg_w * spp * dt.itemsize}")
         seg = np.frombuffer(raw, dt, hh * lay.seg_w * spp).astype(native).reshape(hh, lay.seg_w, spp)
         if lay.predictor == 2:
             seg = np.cumsum(seg, axis=1, dtype=native)
@@ -341,7 +373,8 @@ def decode_device(buf, scene, dev):
     offsets = np.ascontiguousarray(scene.offsets, np.uint64)
     counts = np.ascontiguousarray(scene.counts, np.uint64)
     with torch.cuda.device(dev):
-        raw = torch.frombuffer(bytearray(buf), dtype=torch.uint8).to(dev)      # the file is uploaded once
+        # the file is uploaded once (a window's compact buffer is a bytearray already)
+        raw = torch.frombuffer(buf if isinstance(buf, bytearray) else bytearray(buf), dtype=torch.uint8).to(dev)
         planes = torch.empty((lay.C, lay.H, lay.W), dtype=torch.uint8 if lay.bits == 8 else torch.int16, device=dev)
         status = torch.empty(nseg, dtype=torch.int32, device=dev)
         ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=dev)
@@ -352,7 +385,7 @@ def decode_device(buf, scene, dev):
     bad = np.flatnonzero(st)
     if bad.size:
         i = int(bad[0])
-        raise TiffError(f"segment {i} is damaged: {STATUS_TEXT.get(int(st[i]), st[i])}" +
+        raise TiffError(f"segment {_name(scene, i)} is damaged: {STATUS_TEXT.get(int(st[i]), st[i])}" +
                         (f" ({bad.size} damaged segments in all)" if bad.size > 1 else ""), int(st[i]))
     return planes
 
@@ -387,3 +420,146 @@ def read(path, device=None, ifd=0):
         t = decode_device(buf, scene, _device(device)).cpu().numpy()
         a = t.view(np.uint16) if t.dtype == np.int16 else t
     return a[0] if a.shape[0] == 1 else a
+
+
+# ---------------------------------------------------------------- a window of a scene
+
+class WindowPlan:
+    """What plan_window returns: the segments a window touches and how to hand them to the library as a scene of their own.
+
+        segments  indices into the file's segment table, in the order the sub-layout wants them (TIFF order over the
+                  covered sub-grid; planar = 2: all of band 0, then band 1, ...)
+        layout    the Layout of the covered grid alone: [C, H', W']
+        ranges    the (offset, length) byte ranges of the file that hold those segments, sorted, neighbours merged
+        offsets, counts   the segment table rebased into the compact buffer made of `ranges` one after another
+        crop      (oy, ox): where the window starts inside the cover
+        nbytes    the length of the compact buffer"""
+
+    def __init__(self, window, segments, layout, ranges, offsets, counts, crop):
+        self.window, self.segments, self.layout, self.ranges = window, segments, layout, ranges
+        self.offsets, self.counts, self.crop = offsets, counts, crop
+        self.nbytes = sum(n for _, n in ranges)
+
+    def gather(self, buf):
+        """the compact buffer: `ranges` of buf one after another (never empty: the library takes no null pointer)"""
+        out, at = bytearray(max(self.nbytes, 1)), 0
+        for o, n in self.ranges:
+            out[at:at + n] = buf[o:o + n]
+            at += n
+        return out
+
+
+def plan_window(scene, window):
+    """The plan of reading window = (x0, y0, w, h) of a parsed Scene: host arithmetic on the segment table, no byte of the
+    file is looked at.  The window is checked as codec.check_window checks one."""
+    from .codec import check_window
+    lay = scene.layout
+    x0, y0, w, h = check_window(window, lay.W, lay.H)
+    sw, sh = lay.seg_w, lay.seg_h
+    per_row, rows = -(-lay.W // sw), -(-lay.H // sh)
+    tx0, tx1 = (x0 // sw, -(-(x0 + w) // sw)) if lay.tiled else (0, 1)      # strips: full rows
+    ty0, ty1 = y0 // sh, -(-(y0 + h) // sh)
+    Wc = min(tx1 * sw, lay.W) - tx0 * sw
+    Hc = min(ty1 * sh, lay.H) - ty0 * sh
+    sub = Layout(lay.C, Hc, Wc, lay.bits, lay.big_endian, lay.planar, sw, sh if lay.tiled else min(sh, Hc), lay.tiled,
+                 lay.compression, lay.predictor)
+    segments = [b * per_row * rows + ty * per_row + tx for b in range(lay.C if lay.planar == 2 else 1)
+                for ty in range(ty0, ty1) for tx in range(tx0, tx1)]
+    offs = [int(scene.offsets[i]) for i in segments]
+    cnts = [int(scene.counts[i]) for i in segments]
+    ranges = []      # [offset, end), sorted and merged where one begins at or before the end of the one in front of it
+    for o, c in sorted((o, c) for o, c in zip(offs, cnts) if c):
+        if ranges and o <= ranges[-1][1]:
+            ranges[-1][1] = max(ranges[-1][1], o + c)
+        else:
+            ranges.append([o, o + c])
+    starts = [r[0] for r in ranges]
+    base = np.concatenate([[0], np.cumsum([r[1] - r[0] for r in ranges])]).astype(np.int64) if ranges else np.zeros(1, np.int64)
+    rebased = []
+    for o, c in zip(offs, cnts):
+        k = int(np.searchsorted(starts, o, side="right")) - 1 if c else -1
+        rebased.append(int(base[k]) + o - starts[k] if c else 0)
+    return WindowPlan((x0, y0, w, h), segments, sub, [(a, b - a) for a, b in ranges], np.asarray(rebased, np.uint64),
+                      np.asarray(cnts, np.uint64), (y0 - ty0 * sh, x0 - tx0 * sw))
+
+
+def _window_plain(buf, scene, plan):
+    """The window of an uncompressed strip file, on the host: of every touched strip only the window's rows are read, then
+    the columns are sliced -> numpy [C,h,w]"""
+    lay = scene.layout
+    x0, y0, w, h = plan.window
+    dt = np.dtype(scene.byteorder + ("u1" if lay.bits == 8 else "u2"))
+    spp = 1 if lay.planar == 2 else lay.C
+    row_bytes = lay.W * spp * dt.itemsize
+    rows_y = -(-lay.H // lay.seg_h)
+    out = np.empty((lay.C, h, w), dt.newbyteorder("="))
+    for i in plan.segments:
+        b, ty = divmod(i, rows_y)
+        s0 = ty * lay.seg_h
+        r0, r1 = max(y0, s0), min(y0 + h, s0 + lay.seg_h, lay.H)
+        o, c = int(scene.offsets[i]), int(scene.counts[i])
+        if c < (min(lay.seg_h, lay.H - s0)) * row_bytes:
+            raise TiffError(f"segment {i} is damaged: {STATUS_TEXT[1]}", 1)
+        raw = buf[o + (r0 - s0) * row_bytes:o + (r1 - s0) * row_bytes]
+        part = np.frombuffer(raw, dt, (r1 - r0) * lay.W * spp).reshape(r1 - r0, lay.W, spp)[:, x0:x0 + w, :]
+        dst = out[b:b + 1] if lay.planar == 2 else out
+        dst[:, r0 - y0:r1 - y0, :] = part.transpose(2, 0, 1)
+    return out
+
+
+def _window(buf, path, window, device, ifd, tensor):
+    """read_window_bytes (tensor=True) and read_window (False): a host route leaves the device alone where numpy is asked for"""
+    import torch
+    scene = _parse(buf, path, ifd, False)
+    plan = plan_window(scene, window)
+    lay = plan.layout
+    if lay.compression == COMP_LZW:
+        _old_lzw(buf, path, scene.offsets, scene.counts, plan.segments)
+    (oy, ox), (_, _, w, h) = plan.crop, plan.window
+    a = None
+    if scene.plain_strips():
+        a = _window_plain(buf, scene, plan)
+    else:
+        route = _over_cap(lay, path)
+        sub = Scene(lay, plan.offsets, plan.counts, scene.sample_format, scene.byteorder, names=plan.segments)
+        if route == "host":
+            a = np.ascontiguousarray(_read_host_deflate(plan.gather(buf), sub)[:, oy:oy + h, ox:ox + w])
+    if a is not None:
+        if not tensor:
+            return a
+        return torch.from_numpy(a.view(np.int16) if a.dtype.itemsize == 2 else a).to(_device(device))
+    t = decode_device(plan.gather(buf), sub, _device(device))[:, oy:oy + h, ox:ox + w].contiguous()
+    if tensor:
+        return t
+    t = t.cpu().numpy()
+    return t.view(np.uint16) if t.dtype == np.int16 else t
+
+
+def read_window_bytes(buf, path, window, device=None, ifd=0):
+    """window = (x0, y0, w, h) of IFD `ifd` as a contiguous [C,h,w] tensor on the device, bit for bit that slice of
+    read_device_bytes.  buf: the file as anything that has len() and slices -- bytes, a memory map.  Only the header, the
+    IFD chain, the tag arrays and the segments the window touches are read; those segments alone are uploaded, as one
+    compact buffer, and decoded as a scene of their own (plan_window).  A damaged segment elsewhere is never looked at;
+    one inside raises TiffError under its index in the file."""
+    return _window(buf, path, window, device, ifd, True)
+
+
+def open_map(path):
+    """the file as a read-only memory map (an empty file: its no bytes, which the parser refuses by name)"""
+    import mmap
+    with open(path, "rb") as f:
+        try:
+            return mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ)
+        except ValueError:
+            return f.read()
+
+
+def read_window(path, window, device=None, ifd=0):
+    """read_window_bytes of a file opened as a read-only memory map -> numpy uint8 / uint16 [C,h,w].  An uncompressed strip
+    file and an over-cap Deflate one never touch the device."""
+    buf = open_map(path)
+    try:
+        return _window(buf, path, window, device, ifd, False)
+    finally:
+        if not isinstance(buf, bytes):
+            buf.close()

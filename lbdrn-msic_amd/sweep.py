@@ -48,6 +48,8 @@ def build_parser():
     p.add_argument("-lr", "--lr", type=str, default="0.001", help="kept as text: it is part of the directory name")
     p.add_argument("-bs", "--batch_size", type=int, default=8192)
     p.add_argument("-e", "--epochs", type=int, default=10)
+    p.add_argument("--window", type=int, nargs=4, default=None, metavar=("X0", "Y0", "W", "H"),
+                   help="sweep this part of every image only (encode.py --window)")
     p.add_argument("--summary", action="store_true", help="rank 0 writes the results CSV at the end")
     p.add_argument("--k-in-flight", dest="k_in_flight", type=int, default=1, metavar="N",
                    help="fit up to N of the K points of an image side by side on the GPU (encode.main_k_points); "
@@ -83,20 +85,32 @@ def points(a):
 def common_args(a):
     return ["-D", str(a.D), "-bc", str(a.base_channel), "-nl", str(a.num_layers),
             "-lr", a.lr, "-bs", str(a.batch_size), "-e", str(a.epochs), "-sr", str(a.split_ratio),
-            "-prec", str(a.precision)]
+            "-prec", str(a.precision)] + window_args(a, "--window")
+
+
+def window_args(a, flag):
+    win = getattr(a, "window", None)
+    return [] if win is None else [flag] + [str(v) for v in win]
+
+
+def point_stem(a, image):
+    """encode.scene_name: the image's stem, with --window the window behind it"""
+    stem = os.path.splitext(os.path.basename(image))[0]
+    win = getattr(a, "window", None)
+    return stem if win is None else stem + "_x{}_y{}_w{}_h{}".format(*win)
 
 
 def point_folder(a, image, K):
     # float(lr) -> the directory name encode.py derives from its parsed float (ref run.sh:38 spells it by hand)
-    stem = os.path.splitext(os.path.basename(image))[0]
+    stem = point_stem(a, image)
     return (f"{a.output_dir}/{stem}_r{a.split_ratio}_K{K}_bc{a.base_channel}_nl{a.num_layers}_D{a.D}"
             f"_prec{a.precision}_lr{float(a.lr)}_bs{a.batch_size}_e{a.epochs}")
 
 
 def decode_point(a, image, K):
-    stem = os.path.splitext(os.path.basename(image))[0]
+    stem = point_stem(a, image)
     folder = point_folder(a, image, K)
-    decode.main(["-i", f"{folder}/{stem}.bin", "-org", image], shard_tiles=False)
+    decode.main(["-i", f"{folder}/{stem}.bin", "-org", image] + window_args(a, "--org-window"), shard_tiles=False)
     return folder
 
 
@@ -178,7 +192,7 @@ def main(argv=None):
             failed += err is not None
         print("All files processed.")
         if a.summary:
-            stems = [os.path.splitext(os.path.basename(i))[0] for i in a.images]
+            stems = [point_stem(a, i) for i in a.images]
             results_summary.save_to_csv(
                 ["-o", a.output_dir, "-sr", str(a.split_ratio), "-bc", str(a.base_channel), "-nl", str(a.num_layers),
                  "-D", str(a.D), "-prec", str(a.precision), "-lr", a.lr, "-bs", str(a.batch_size),
