@@ -20,6 +20,13 @@ With it, `--out-overviews auto|N [--out-resampling average|nearest] [--out-nodat
 from the reconstruction where it lies (lbdrn_hip.pyramid), and `--out-georef FILE` copies FILE's georeferencing tags onto the
 output.  No log record changes.
 
+A file written with `encode.py --keep-tags` carries the scene's georeferencing and nodata tags behind everything else
+(container.unpack_geo_trailer): they go onto the output TIFF by default -- as stored for a whole decode, moved to the window's
+origin for `--window` (lbdrn_hip.geotags.shift) -- with `--out-compress` through the same `geo=` option, without it through
+raster_io.write_raster(path, image, geo=tags), and one record says so (`Tags: <n> tags restored`).  `--out-georef FILE` still
+copies FILE's tags verbatim and wins; `--no-tags` ignores the chunk; a .npy output gets none.  With `--out-overviews` and no
+`--out-nodata`, a stored GDAL_NODATA that is an integer sample value is the overviews' nodata.
+
 `-org ORG --metrics [--metrics-peak P] [--metrics-json FILE]` adds, behind the `PSNR:` / `Max error:` record, one `Quality band c:`
 line per band and one `Quality:` line for the raster (lbdrn_hip.quality.compare: error statistics, SSIM and the spectral angle,
 computed on the GPU).  The other records are what they are without the flag."""
@@ -33,7 +40,7 @@ import numpy as np
 import torch
 
 import logger
-from lbdrn_hip import codec, container, ops, raster_io, shard
+from lbdrn_hip import codec, container, geotags, ops, raster_io, shard
 from lbdrn_hip.features import FeatCfg
 from LBDRNdataset import tile_windows, write_tiff_with_gdal
 
@@ -46,11 +53,11 @@ def read_image_header(bitstream):
     return container.unpack_header(bitstream)
 
 
-def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=None, out=None):
+def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=None, out=None, geo=None):
     """Decode one image or tile from the front of `bitstream`; returns the remaining bytes
     (ref decode.py:56-141).  layer: the tile's residual body (LBR1), applied to the reconstruction in HBM.  out: the
     options of --out-compress (raster_io.write_raster_device); the raster is then written from the reconstruction where it
-    lies, without a host copy of it."""
+    lies, without a host copy of it.  geo: the tags for a raster written without those options (write_plain)."""
     nn_payload, bitstream = bitstream[:nn_bytes], bitstream[nn_bytes:]
     base_payload, bitstream = bitstream[:base_bytes], bitstream[base_bytes:]
     base = container.decode_base(base_payload, device=DEVICE, keep_on_device=True)   # ref decode.py:69-73
@@ -77,28 +84,52 @@ def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=N
         image = ops.from_device_u16(codec.residual_apply(layer, rec.contiguous()))
     test.last_image = image
     if write:
-        write_tiff_with_gdal(recon_path, image)
+        write_plain(recon_path, image, geo)
         logger.log.info(f"Recon: {recon_path}")
     return bitstream
 
 
-def out_options(args):
+def write_plain(path, image, geo):
+    """today's writer; with tags to restore, the same array through raster_io.write_raster(geo=): lbdrn_hip.tiff_write at
+    compression "none" (GDAL's writer is never asked to carry them)"""
+    if geo:
+        raster_io.write_raster(path, image, geo=geo, device=DEVICE)
+    else:
+        write_tiff_with_gdal(path, image)
+
+
+def stored_tags(args, bitstream, path, window=None):
+    """The tags to put on the raster at `path` from the file's geo-tag chunk: as stored, or moved to the window's origin;
+    None for a file without the chunk, under --no-tags, where --out-georef names the tags instead, and for a .npy output."""
+    if args.no_tags:
+        return None
+    tags = container.unpack_geo_trailer(bitstream)
+    if not tags or args.out_georef is not None or path.endswith(".npy"):
+        return None
+    return tags if window is None else geotags.shift(tags, window[0], window[1])
+
+
+def out_options(args, geo=None):
     """the raster_io.write_raster_device options --out-compress / --out-tile / --out-overviews / --out-resampling / --out-nodata /
-    --out-georef ask for; None: today's writer"""
+    --out-georef ask for; None: today's writer.  geo: the stored tags to restore (stored_tags): they ride the `geo` option,
+    and their GDAL_NODATA, where it is an integer sample value, is the overviews' nodata unless --out-nodata names one."""
     if args.out_compress is None:
         return None
     out = {"compress": args.out_compress, "tile": args.out_tile}
     if args.out_overviews is not None:
-        out.update(overviews=args.out_overviews, resampling=args.out_resampling or "average", nodata=args.out_nodata)
+        nodata = args.out_nodata if args.out_nodata is not None else geotags.stored_nodata(geo, 16)
+        out.update(overviews=args.out_overviews, resampling=args.out_resampling or "average", nodata=nodata)
     if args.out_georef is not None:
         out["geo"] = raster_io.read_geo_tags(args.out_georef) or None
+    elif geo:
+        out["geo"] = geo
     return out
 
 
-def write_merged(path, image, out):
+def write_merged(path, image, out, geo=None):
     """a host array (merged tiles, gathered ranks) to its raster: uploaded once where --out-compress is given"""
     if out is None:
-        write_tiff_with_gdal(path, image)
+        write_plain(path, image, geo)
     else:
         raster_io.write_raster_device(path, ops.to_device_u16(image, DEVICE) if image.dtype == np.uint16 else
                                       torch.from_numpy(np.ascontiguousarray(image)).to(DEVICE), **out)
@@ -147,8 +178,9 @@ def decode_window_main(args, rank, world):
     # decode_window_pieces applies a layer by default; only --no-enhancement has anything to say to it
     more = {"enhance": False} if args.no_enhancement else {}
     _, parts = codec.decode_window_pieces(bitstream, args.window, device=DEVICE, take=lambda k, piece: k % world == rank, **more)
-    out = out_options(args)
     recon_path = args.out_path or f"{dirname}/{basename[:-4]}_recon_x{x0}_y{y0}_w{w}_h{h}.tif"
+    geo = stored_tags(args, bitstream, recon_path, (x0, y0, w, h))
+    out = out_options(args, geo)
     on_device = out is not None and world == 1      # the pieces stay in HBM, are put together there and written from there
     if on_device:
         image = None
@@ -170,8 +202,10 @@ def decode_window_main(args, rank, world):
                 if image is None:
                     image = np.zeros((rec.shape[0], h, w), rec.dtype)
                 image[:, oy:oy + rec.shape[1], ox:ox + rec.shape[2]] = rec
-            write_merged(recon_path, image, out)
+            write_merged(recon_path, image, out, geo)
         logger.log.info(f"Recon: {recon_path}")
+        if geo:
+            logger.log.info(f"Tags: {len(geo)} tags restored")
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
         if args.org_path is not None:
             org_img = raster_io.read_raster(args.org_path, window=(x0, y0, w, h))      # the window of the original alone
@@ -209,6 +243,9 @@ def main(argv=None, shard_tiles=None):
     p.add_argument("--out-georef", dest="out_georef", type=str, default=None, metavar="FILE",
                    help="with --out-compress: copy FILE's georeferencing tags onto the output (the original scene, or any raster "
                         "on the same grid)")
+    p.add_argument("--no-tags", dest="no_tags", action="store_true",
+                   help="ignore the georeferencing tags of a file that carries them (encode.py --keep-tags): the raster a file "
+                        "without them decodes to")
     p.add_argument("--metrics", action="store_true",
                    help="with -org: per-band error statistics, SSIM and the spectral angle, compared on the GPU (lbdrn_hip.quality)")
     p.add_argument("--metrics-peak", dest="metrics_peak", type=float, default=None, metavar="P",
@@ -288,8 +325,10 @@ def main(argv=None, shard_tiles=None):
     if layer is not None:
         logger.log.info(f"Residual layer: max error {layer[0]}")
     bodies = layer[1] if layer is not None else [None] * (split_ratio * split_ratio)
-    bitstream = bitstream[n_hdr:]
     recon_path = f"{dirname}/{basename[:-4]}_recon.tif"
+    geo = stored_tags(args, bitstream, recon_path)
+    out = out_options(args, geo) if rank == 0 else None      # (rank 0 writes)
+    bitstream = bitstream[n_hdr:]
     if split_ratio > 1:
         decoded, offset = [], 0
         for t, (i, j, x0, y0, w, h) in enumerate(tile_windows(width, height, split_ratio)):
@@ -305,10 +344,12 @@ def main(argv=None, shard_tiles=None):
                 if merged is None:
                     merged = np.zeros((tiles[t].shape[0], height, width), tiles[t].dtype)
                 merged[:, y0:y0 + h, x0:x0 + w] = tiles[t]
-            write_merged(recon_path, merged, out_options(args))
+            write_merged(recon_path, merged, out, geo)
     elif rank == 0:
-        test(bitstream, dirname, filename, nn_list[0], base_list[0], layer=bodies[0], out=out_options(args))
+        test(bitstream, dirname, filename, nn_list[0], base_list[0], layer=bodies[0], out=out, geo=geo)
     if rank == 0:
+        if geo:
+            logger.log.info(f"Tags: {len(geo)} tags restored")
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
         if args.org_path is not None:
             org_img = (raster_io.read_raster(args.org_path) if args.org_window is None else

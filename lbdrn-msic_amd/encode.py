@@ -4,6 +4,7 @@ fused HIP kernels (lbdrn_hip.codec.fit_image) instead of DataLoader + ignite + a
 
 Bitstream: header | for each tile (row-major): network payload | MSB payload   (ref encode.py:29-36)
            [| residual-layer trailer, with --max-error T: container.pack_residual_trailer]
+           [| geo-tag chunk, with --keep-tags on a source that has tags: container.pack_geo_trailer]
 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N encode.py ... -sr S` fits the S*S tiles of the
 image round-robin on N GPUs (one process per GPU, no exchange during the fits) and rank 0 assembles the
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 
 import logger
-from lbdrn_hip import codec, container, raster_io, shard
+from lbdrn_hip import codec, container, geotags, raster_io, shard
 from lbdrn_hip.features import FeatCfg
 from LBDRNdataset import tile_windows
 
@@ -190,7 +191,25 @@ def build_parser():
     p.add_argument("--max-error", dest="max_error", type=int, default=None, metavar="T",
                    help="append a residual layer that bounds |original - reconstruction| by T on every sample (0: lossless); "
                         "default: no layer")
+    p.add_argument("--keep-tags", dest="keep_tags", action="store_true", default=argparse.SUPPRESS,
+                   help="carry the input's georeferencing and nodata tags in the .bin (moved to the window with --window): "
+                        "decode.py puts them on its raster.  Default: the file the reference's reader expects, nothing behind it")
     return p
+
+
+def scene_tags(args, path, window):
+    """--keep-tags: (the geo-tag chunk to append as the last thing of the .bin -- b"" for a source without tags: a .npy
+    array, a TIFF that has none --, its `Tags:` record), else (b"", None).  With a window the tags are those of the crop
+    (geotags.shift).  Reads the header, the IFD and the tags' values of the source, no pixel."""
+    if not getattr(args, "keep_tags", False):      # (absent without the flag, like `window`: the records of such a run stay)
+        return b"", None
+    tags = raster_io.read_geo_tags(path)
+    if window is not None:
+        tags = geotags.shift(tags, window[0], window[1])
+    if not tags:
+        return b"", "Tags: none"
+    chunk = container.pack_geo_trailer(tags)
+    return chunk, f"Tags: {len(tags)} tags, {len(chunk)} bytes"
 
 
 def scene_name(args):
@@ -288,6 +307,8 @@ def main(argv=None, shard_tiles=None):
     else:
         logger.create_logger(args.output_dir, "", log_file_only=True)
     start_time = time.time()
+    # --keep-tags: rank 0 alone opens the tags, before anything is fitted (a source they cannot be read from ends the run here)
+    geo_chunk, geo_record = scene_tags(args, org_path, window) if rank == 0 else (b"", None)
     tile_reads = tile_reads_wanted() and args.split_ratio > 1
     if tile_reads:
         img = None
@@ -348,6 +369,9 @@ def main(argv=None, shard_tiles=None):
                 f.write(base)
             if args.max_error is not None:      # behind everything the header lists: older readers stop before it
                 f.write(container.pack_residual_trailer(args.max_error, [rec[4] for rec in tiles]))
+            f.write(geo_chunk)                  # --keep-tags: the last thing in the file, behind the layer where there is one
+        if geo_record is not None:
+            logger.log.info(geo_record)
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
     if world > 1:
         shard.finish()
@@ -415,6 +439,7 @@ def main_k_points(argv, Ks):
         return outcome
     start_time = time.time()
     try:
+        geo_chunk, geo_record = scene_tags(base, org_path, window)      # --keep-tags: read once, carried by every K's file
         tile_reads = tile_reads_wanted() and base.split_ratio > 1
         if tile_reads:
             img = None
@@ -474,6 +499,9 @@ def main_k_points(argv, Ks):
                     f.write(base_payload)
                 if a.max_error is not None:
                     f.write(container.pack_residual_trailer(a.max_error, [rec[2] for rec in tiles_out]))
+                f.write(geo_chunk)
+            if geo_record is not None:
+                logger.log.info(geo_record)
             # this point's share of the reading and fitting all points did together, plus its own reporting and packing
             logger.log.info(f"Time elapsed: {shared_seconds + time.time() - t_point}")
             outcome[K] = None

@@ -1,5 +1,6 @@
 """.bin container of the codec: header (a12) + per tile the network payload and the MSB payload (+ behind them, with
-encode.py --max-error, the residual-layer trailer: pack_residual_trailer).
+encode.py --max-error, the residual-layer trailer: pack_residual_trailer; and last of all, with encode.py --keep-tags, the
+geo-tag chunk: pack_geo_trailer).
 
 Header layout (ref encode.py:37-64, decode.py:25-53), big-endian:
   hdr_len:u8  split_ratio:u8  width:u16  height:u16  (K<<4)|D:u8  (log2(bc)<<4)|nl:u8
@@ -122,14 +123,18 @@ def pack_residual_trailer(tau, bodies):
     return out + b"".join(bytes(b) for b in bodies)
 
 
-def unpack_residual_trailer(buf):
-    """-> (tau, [LBR1 body per tile]) of a .bin with a residual layer, None for a file that ends behind its listed payloads.
-    Anything else behind them -- another magic, a newer version, sizes that do not fill the file -- raises."""
+def _trailers(buf):
+    """((tau, bodies) or None, geo tags or None, where the file ends without the chunk) from everything behind the listed
+    payloads: nothing, a residual-layer trailer, a geo-tag chunk, or the trailer followed by exactly one chunk.  Anything
+    else raises."""
+    from . import geotags
     off = residual_trailer_offset(buf)
     if len(buf) == off:
-        return None
+        return None, None, off
     if len(buf) < off:
         raise ValueError(f"bitstream of {len(buf)} bytes is shorter than the {off} its header lists")
+    if bytes(buf[off:off + 4]) == GEO_TRAILER_MAGIC:      # no layer: the chunk fills the rest (a second one, an 'LBRT' or any
+        return None, geotags.unpack(buf[off:]), off       # byte behind it is a size that does not match)
     tiles = buf[1] * buf[1]
     if len(buf) < off + 7 + 4 * tiles or bytes(buf[off:off + 4]) != RESID_TRAILER_MAGIC:
         raise ValueError(f"{len(buf) - off} bytes behind the listed payloads are not a residual-layer trailer")
@@ -138,13 +143,51 @@ def unpack_residual_trailer(buf):
         raise ValueError(f"residual-layer trailer version {version}: written by a newer version of this package")
     sizes = struct.unpack_from(f">{tiles}I", buf, off + 7)
     pos = off + 7 + 4 * tiles
-    if pos + sum(sizes) != len(buf):
+    if pos + sum(sizes) > len(buf):
         raise ValueError(f"residual-layer trailer lists {sum(sizes)} bytes of bodies, the file holds {len(buf) - pos}")
     bodies = []
     for n in sizes:
         bodies.append(bytes(buf[pos:pos + n]))
         pos += n
-    return tau, bodies
+    if pos == len(buf):
+        return (tau, bodies), None, pos
+    try:
+        return (tau, bodies), geotags.unpack(buf[pos:]), pos
+    except ValueError as e:
+        raise ValueError(f"residual-layer trailer lists {sum(sizes)} bytes of bodies, the file holds {len(buf) - pos + sum(sizes)}, "
+                         f"and what follows them is no geo-tag chunk ({e})") from None
+
+
+def unpack_residual_trailer(buf):
+    """-> (tau, [LBR1 body per tile]) of a .bin with a residual layer, None for a file that ends behind its listed payloads.
+    Anything else behind them -- another magic, a newer version, sizes that do not fill the file -- raises.  A geo-tag chunk
+    (pack_geo_trailer) behind the bodies, or behind the payloads of a file without a layer, changes nothing: the result is
+    that of the file with the chunk cut off."""
+    return _trailers(buf)[0]
+
+
+# ---------------------------------------------------------------- geo-tag trailer (encode.py --keep-tags)
+
+GEO_TRAILER_MAGIC = b"LBGT"
+
+
+def pack_geo_trailer(tags):
+    """The 'LBGT' chunk of a scene's georeferencing and nodata tags -- [(tag, type, count, little-endian value bytes)], what
+    tiff.read_geo_tags returns -- to append as the LAST thing of a .bin: behind the residual-layer trailer where there is
+    one, otherwise directly behind the listed payloads.  lbdrn_hip/geotags.py has the layout.  The header is untouched."""
+    from . import geotags
+    return geotags.pack(tags)
+
+
+def unpack_geo_trailer(buf):
+    """-> the tag list of a .bin that carries the chunk, None for a file without it.  What unpack_residual_trailer refuses
+    is refused here too; so are a chunk in front of the residual-layer trailer, two chunks and any byte behind the chunk."""
+    return _trailers(buf)[1]
+
+
+def strip_geo_trailer(buf):
+    """The file without its geo-tag chunk (a residual-layer trailer stays); a file without one as it is."""
+    return bytes(buf[:_trailers(buf)[2]])
 
 
 # ---------------------------------------------------------------- weights payload (a10)

@@ -210,12 +210,17 @@ def _read_window(path, overview, window, device):
 
 def read_geo_tags(path):
     """The georeferencing tags of a TIFF's first IFD as [(tag, type, count, little-endian value bytes)] -- what write_raster
-    takes as `geo`; [] for a file without them and for a .npy array."""
+    takes as `geo`; [] for a file without them and for a .npy array.  Read from a read-only memory map: only the header,
+    the IFD and the tags' values are touched, whatever the size of the scene."""
     if path.endswith(".npy"):
         return []
     from . import tiff
-    with open(path, "rb") as f:
-        return tiff.read_geo_tags(f.read(), path)
+    buf = tiff.open_map(path)
+    try:
+        return tiff.read_geo_tags(buf, path)
+    finally:
+        if not isinstance(buf, bytes):
+            buf.close()
 
 
 def _wants_writer(path, compress, tile, rows_per_strip, planar, predictor, overviews=None, resampling="average", nodata=None, geo=None):
@@ -242,13 +247,14 @@ def _new_options(overviews, resampling, nodata, geo):
 
 
 def write_raster(path, array, compress=None, tile=None, rows_per_strip=None, planar=2, predictor=None, overviews=None,
-                 resampling="average", nodata=None, geo=None):
+                 resampling="average", nodata=None, geo=None, device=None):
     """array [C,H,W]: uint8 / uint16 / float32 / float64 (ref write_tiff_with_gdal).  With every option at its default the
     file is what it always was: one uncompressed strip per band.  compress="deflate" (defaults: 256 x 256 tiles, planar,
     predictor 2), or compress=None with tile= or rows_per_strip=, writes through lbdrn_hip.tiff_write: the array is uploaded
     and its segments are built and compressed on the GPU.  Integer rasters only.  overviews="auto" or a count adds that many
     overview levels, reduced on the GPU (resampling "average" or "nearest", nodata a value that does not enter an average);
-    geo -- what read_geo_tags returns -- is copied onto the full-resolution IFD.  Either goes through the same writer."""
+    geo -- what read_geo_tags returns -- is copied onto the full-resolution IFD.  Either goes through the same writer, on
+    `device` (default "cuda:0")."""
     if array.dtype.type not in (np.uint8, np.uint16, np.float32, np.float64):
         raise ValueError("Unsupported data type in this function")
     if _wants_writer(path, compress, tile, rows_per_strip, planar, predictor, overviews, resampling, nodata, geo):
@@ -256,7 +262,7 @@ def write_raster(path, array, compress=None, tile=None, rows_per_strip=None, pla
             raise ValueError(f"{array.dtype} rasters are written uncompressed only: compress, tile, rows_per_strip, planar and "
                              "predictor are for uint8 / uint16 (the reader reads no compressed float raster either)")
         from . import tiff_write
-        tiff_write.write(path, array, compress or "none", tile, rows_per_strip, planar, predictor,
+        tiff_write.write(path, array, compress or "none", tile, rows_per_strip, planar, predictor, device,
                          **_new_options(overviews, resampling, nodata, geo))
         return
     if path.endswith(".npy"):

@@ -17,6 +17,8 @@ fi
 # K_IN_FLIGHT=N (default: unset = 1) is sweep.py's --k-in-flight N: a process fits up to N of the K points of an image side by
 # side instead of one after another (same files; meant for PER_GPU=1, where a lone fit leaves half of the chip idle).
 if [ -n "${K_IN_FLIGHT}" ]; then set -- "$@" --k-in-flight "${K_IN_FLIGHT}"; fi
+# KEEP_TAGS=1 is sweep.py's --keep-tags: every .bin carries its image's georeferencing and nodata tags.
+if [ "${KEEP_TAGS:-0}" = "1" ]; then set -- "$@" --keep-tags; fi
 NPROC=$(( ${NGPU:-1} * ${PER_GPU:-2} ))
 if [ "${PER_GPU:-2}" -gt 1 ]; then export LBDRN_DEVICE_SHARED="${LBDRN_DEVICE_SHARED:-1}" LBDRN_OVERLAP_EVAL="${LBDRN_OVERLAP_EVAL:-0}"; fi
 if [ "${NPROC}" -gt 1 ]; then
