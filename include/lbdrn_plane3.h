@@ -4,7 +4,9 @@
  * LBB3 is LBB2 (csrc/plane_codec.hip) with two changes: the unit of work holds all bands of its pixels, so that a band can
  * be predicted from the band before it, and a band of a pass picks one of eight modes instead of four.  The entropy stage
  * -- adaptive Golomb-Rice per lane with zero-group flags, the 32-bit words of a unit interleaved in the order the decoding
- * wave asks for them -- is LBB2's.  container.py frames the body as b"LBB3" + pack(">BHII", code, C, H, W) + body.
+ * wave asks for them -- is LBB2's, and one text with it: both are built from csrc/plane_lane.inc (predictors, fold, lane
+ * coder) and csrc/plane_wave.hpp (the wave's walk).  For one band and S >= H a unit is an LBB2 strip, and the body behind
+ * the header is LBB2's body byte for byte.  container.py frames the body as b"LBB3" + pack(">BHII", code, C, H, W) + body.
  *
  * ---------------------------------------------------------------------------------------------------------- the format
  *

@@ -1,10 +1,13 @@
 // liblbdrn_plane3.so (include/lbdrn_plane3.h): "LBB3", the lossless payload of the MSB planes with inter-band prediction,
-// coded and decoded on the GPU.  The format's text (geometry, predictors and modes, fold, lane coder, mode words, header
-// and table validation) is csrc/plane3.inc, shared with the host tests; the full description is in the header.
+// coded and decoded on the GPU.  The format's text (geometry, modes, mode words, header and table validation, and through
+// csrc/plane_lane.inc the predictors, the fold and the lane coder) is csrc/plane3.inc, shared with the host tests; the full
+// description is in the header.
 //
 // LBB3 is LBB2 (csrc/plane_codec.hip) with another unit -- 64 columns x S rows x all C bands instead of 64 columns x the full
 // height x one band -- and eight modes instead of four: each of LBB2's spatial predictors either plain or with the band
-// before's residual at the same pixel carried over.  The entropy stage and the word hand-out are LBB2's.
+// before's residual at the same pixel carried over.  The entropy stage and the word hand-out are LBB2's, one text for
+// both: plane_lane.inc, and plane_wave.hpp for the bit writer, the replay and the hand-out.  What is here is LBB3's own: the
+// unit, two pixel windows, the packed mode words, a lane's coder state of a band parked in LDS.
 //
 //   k_p3_encode    one 64-lane workgroup per unit.  Phase A walks pass -> band: stage the band's 65 x 64 window in LDS beside
 //                  the band before's (two windows, used in turn), the eight residual sums (wave reduction), code the lane's
@@ -22,6 +25,7 @@
 #include "error_buffer.inc"
 #include "../../include/lbdrn_plane3.h"
 #include "plane3.inc"
+#include "plane_wave.hpp"
 
 namespace lbdrn {
 
@@ -68,17 +72,6 @@ static void carve_p3(const plane3::Geom& g, void* ws, P3Ws* w, bool decoder)
     w->total = (size_t)(p - (char*)ws);
 }
 
-__device__ __forceinline__ uint32_t p3_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int p3_lanes_below(unsigned long long mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // ------------------------------------------------------------------ encoder
 
 __global__ void __launch_bounds__(P3_T) k_p3_encode(const uint16_t* __restrict__ planes, plane3::Geom g, P3Sizes z, P3Ws w,
@@ -100,9 +93,7 @@ __global__ void __launch_bounds__(P3_T) k_p3_encode(const uint16_t* __restrict__
     uint32_t* wout = w.words + (size_t)unit * z.capw;
 
     // ---- phase A: private streams
-    unsigned long long acc = 0;
-    int nb = 0;
-    size_t pwords = 0;
+    BitWriter bits;
     for (int p = 0; p < np; ++p) {
         const int rows = min(P3_T, un.uh - p * P3_T);
         const int ru = p * P3_T + lane;
@@ -133,10 +124,10 @@ __global__ void __launch_bounds__(P3_T) k_p3_encode(const uint16_t* __restrict__
                     }
                 }
             int mode = 0;
-            uint32_t best = p3_wave_sum(sum[0]);
+            uint32_t best = wave_sum(sum[0]);
 #pragma unroll
             for (int m = 1; m < plane3::NMODES; ++m) {
-                const uint32_t s = p3_wave_sum(sum[m]);
+                const uint32_t s = wave_sum(sum[m]);
                 if ((c != 0 || m < plane3::NSPATIAL) && s < best) { best = s; mode = m; }
             }
             if (lane == 0) gmodes[p * C + c] = mode;
@@ -164,70 +155,36 @@ __global__ void __launch_bounds__(P3_T) k_p3_encode(const uint16_t* __restrict__
                     uint32_t code;
                     const int len = plane3::encode_symbol(st, &vrow[lane][0], j, tw, &code);
                     lensw[lane][j] = (uint8_t)len;
-                    if (len) {
-                        acc = (acc << len) | code;
-                        nb += len;
-                        if (nb >= 32) {
-                            priv[pwords++] = (uint32_t)(acc >> (nb - 32));
-                            nb -= 32;
-                        }
-                    }
+                    bits.put(priv, code, len);
                 }
             }
             stA[c][lane] = st.A; stN[c][lane] = st.N;
             __syncthreads();
-            {   // the band's symbol lengths of this pass, 4 KB, coalesced
-                const uint32_t* src = reinterpret_cast<const uint32_t*>(&lensw[0][0]);
-                uint32_t* dst = reinterpret_cast<uint32_t*>(glens + (size_t)(p * C + c) * P3_T * P3_T);
-                for (int idx = lane; idx < P3_T * P3_T / 4; idx += P3_T) dst[idx] = src[idx];
-            }
+            copy_lens_tile(glens + (size_t)(p * C + c) * P3_T * P3_T, &lensw[0][0], lane);
         }
     }
-    if (lane < un.uh) priv[pwords++] = nb ? (uint32_t)(acc << (32 - nb)) : 0u;  // tail, zero padded
+    if (lane < un.uh) bits.tail(priv);
     __threadfence_block();
     __syncthreads();
 
     // ---- phase B: the decoder's request order
     const int mw = plane3::mode_words(C);
     if (lane < C) wout[lane] = head[lane];
-    uint32_t nw = (uint32_t)C;
-    int fill = 0;
-    size_t taken = 0;
+    Replay rp;
+    rp.nw = (uint32_t)C;
     for (int p = 0; p < np; ++p) {
         const int rows = min(P3_T, un.uh - p * P3_T);
         if (lane < mw) {
             uint32_t word = 0;
             for (int c = lane * plane3::MODES_PER_WORD; c < min(C, (lane + 1) * plane3::MODES_PER_WORD); ++c)
                 word = plane3::put_mode(word, c, gmodes[p * C + c]);
-            wout[nw + lane] = word;
+            wout[rp.nw + lane] = word;
         }
-        nw += (uint32_t)mw;
-        for (int c = 0; c < C; ++c) {
-            __syncthreads();
-            {
-                const uint32_t* src = reinterpret_cast<const uint32_t*>(glens + (size_t)(p * C + c) * P3_T * P3_T);
-                uint32_t* dst = reinterpret_cast<uint32_t*>(&lensw[0][0]);
-                for (int idx = lane; idx < P3_T * P3_T / 4; idx += P3_T) dst[idx] = src[idx];
-            }
-            const size_t taken0 = taken;
-            for (int u = 0; u <= P3_T; ++u) pwin[lane][u] = taken0 + u < pwords ? priv[taken0 + u] : 0u;
-            __syncthreads();
-            for (int d = 0; d < rows + tw - 1; ++d) {
-                const int j = d - lane;
-                const bool active = lane < rows && j >= 0 && j < tw;
-                const bool need = active && fill < 32;
-                const unsigned long long mask = __ballot(need);
-                if (need) {
-                    wout[nw + p3_lanes_below(mask)] = pwin[lane][taken - taken0];
-                    taken += 1;
-                    fill += 32;
-                }
-                nw += (uint32_t)__popcll(mask);
-                if (active) fill -= lensw[lane][j];
-            }
-        }
+        rp.nw += (uint32_t)mw;
+        for (int c = 0; c < C; ++c)
+            rp.band(glens + (size_t)(p * C + c) * P3_T * P3_T, priv, bits.pwords, rows, tw, lane, lensw, pwin, wout);
     }
-    if (lane == 0) counts[unit] = nw;
+    if (lane == 0) counts[unit] = rp.nw;
 }
 
 // counts[0 .. n) -> offsets[0 .. n]: the exclusive sum and, behind it, the total
@@ -307,9 +264,8 @@ __global__ void __launch_bounds__(P3_T) k_p3_decode(const uint32_t* __restrict__
         st.init(k0, z0);
         stA[c][lane] = st.A; stN[c][lane] = st.N;
     }
-    unsigned long long buf = 0;
-    int nb = 0;
-    uint32_t cur = (uint32_t)C;
+    WordReader rd;
+    rd.cur = (uint32_t)C;
     for (int p = 0; p < np; ++p) {
         const int rows = min(P3_T, un.uh - p * P3_T);
         const int ru = p * P3_T + lane;
@@ -317,16 +273,15 @@ __global__ void __launch_bounds__(P3_T) k_p3_decode(const uint32_t* __restrict__
 #pragma unroll
         for (int i = 0; i < 2; ++i)
             if (i < mw) {
-                if (cur + i < nws) mword[i] = ws[cur + i]; else bad = true;
+                if (rd.cur + i < nws) mword[i] = ws[rd.cur + i]; else bad = true;
                 if (!plane3::mode_word_ok(mword[i], i, C)) { bad = true; mword[i] = 0u; }
             }
-        cur += (uint32_t)mw;
+        rd.cur += (uint32_t)mw;
         for (int c = 0; c < C; ++c) {
             const int cb = c & 1;
             const int mode = plane3::get_mode(c < plane3::MODES_PER_WORD ? mword[0] : mword[1], c);
-            const uint32_t cur0 = cur;
             __syncthreads();
-            for (int idx = lane; idx < P3_WWIN; idx += P3_T) wwin[idx] = (uint64_t)cur0 + idx < nws ? ws[cur0 + idx] : 0u;
+            rd.stage(wwin, P3_WWIN, ws, nws, lane);
             if (p && lane < tw) px[cb][0][lane] = above[c][lane];
             __syncthreads();
             plane3::Lane st;
@@ -335,20 +290,11 @@ __global__ void __launch_bounds__(P3_T) k_p3_decode(const uint32_t* __restrict__
             for (int d = 0; d < rows + tw - 1; ++d) {
                 const int j = d - lane;
                 const bool active = lane < rows && j >= 0 && j < tw;
-                const bool need = active && nb < 32;
-                const unsigned long long mask = __ballot(need);
-                if (need) {
-                    const uint32_t idx = cur + (uint32_t)p3_lanes_below(mask);
-                    if (idx >= nws) bad = true;
-                    buf |= (unsigned long long)wwin[min(idx - cur0, (uint32_t)P3_WWIN - 1)] << (32 - nb);
-                    nb += 32;
-                }
-                cur += (uint32_t)__popcll(mask);
+                if (!rd.refill(active, wwin, P3_WWIN, nws)) bad = true;
                 if (active) {
                     int len;
-                    const uint32_t v = plane3::decode_symbol(st, (uint32_t)(buf >> 32), j, tw, &len);
-                    buf <<= len;
-                    nb -= len;
+                    const uint32_t v = plane3::decode_symbol(st, rd.top(), j, tw, &len);
+                    rd.drop(len);
                     const int a = j ? px[cb][lane + 1][j - 1] : 0, b = ru ? px[cb][lane][j] : 0, dd = (j && ru) ? px[cb][lane][j - 1] : 0;
                     int pv = 0, pa = 0, pb = 0, pd = 0;
                     if (mode >= plane3::NSPATIAL) {
@@ -366,7 +312,7 @@ __global__ void __launch_bounds__(P3_T) k_p3_decode(const uint32_t* __restrict__
             if (lane < tw) above[c][lane] = px[cb][P3_T][lane];   // the next pass's row above (unused after a short pass)
         }
     }
-    if (cur != nws) bad = true;
+    if (rd.cur != nws) bad = true;
     if (bad) atomicOr(status, 1);
 }
 

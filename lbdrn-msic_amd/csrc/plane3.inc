@@ -1,27 +1,26 @@
 // The LBB3 payload's format text (include/lbdrn_plane3.h), written once for the device and the host: geometry and bounds,
-// the predictors and the eight modes, the fold, the lane coder in both directions, the mode words, the header and the
-// host-side validation of a body's table.  csrc/plane3.hip compiles it for the kernels, tests/plane3_host_shim.cpp and
-// tests/plane3_damage_main.cpp compile the same text with a host compiler.  No state, no allocation, no I/O.
-//
-// The predictors, the fold and the lane coder are LBB2's (csrc/plane_codec.hip), copied: LBB2's bytes are pinned by its own
-// tests and must not move with this file.
+// the eight modes, the mode words, the header and the host-side validation of a body's table.  The spatial predictors,
+// the fold and the lane coder in both directions are csrc/plane_lane.inc, the one text LBB2 (csrc/plane_codec.hip) is built
+// from as well; their names are reachable as plane3:: too.  csrc/plane3.hip compiles this file for the kernels,
+// tests/plane3_host_shim.cpp and tests/plane3_damage_main.cpp compile the same text with a host compiler.  No state, no
+// allocation, no I/O.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define P3_HD __host__ __device__ inline
-#else
-#define P3_HD inline
-#endif
+#include "plane_lane.inc"
+
+#define P3_HD PL_HD
 
 namespace plane3 {
 
-constexpr int T = 64;                 // columns of a unit = lanes = rows of a pass
-constexpr int NSPATIAL = 4;           // MED / mean / plane / mix
-constexpr int NMODES = 8;             // each of them plain or differential
-constexpr int QESC = 15;              // unary length that announces a raw 16-bit value
+using plane_lane::T, plane_lane::NSPATIAL, plane_lane::QESC;
+using plane_lane::inner, plane_lane::predict, plane_lane::fold, plane_lane::unfold;
+using plane_lane::Lane, plane_lane::start_parameters, plane_lane::head_word, plane_lane::read_head_word;
+using plane_lane::encode_symbol, plane_lane::leading_ones, plane_lane::decode_symbol;
+
+constexpr int NMODES = 8;             // each of the four spatial predictors plain or differential
 constexpr int MAX_C = 16;
 constexpr int MAX_SIDE = 1 << 20;
 constexpr int WRITER_S = 256;         // rows of a unit as lbdrn_plane3_encode cuts them
@@ -72,23 +71,6 @@ P3_HD size_t body_bound(const Geom& g)
 
 // ---------------------------------------------------------------- prediction
 
-P3_HD int inner(int a, int b, int d, int m)
-{
-    if (m == 0) {
-        const int mn = a < b ? a : b, mx = a < b ? b : a;
-        return d >= mx ? mn : (d <= mn ? mx : a + b - d);
-    }
-    if (m == 1) return (a + b) >> 1;
-    if (m == 2) return a + b - d;
-    return ((3 * (a + b) - 2 * d + (1 << 20)) >> 2) - (1 << 18);
-}
-// ru: row in the unit, j: column in the unit; a left, b up, d up-left
-P3_HD int predict(int ru, int j, int a, int b, int d, int m)
-{
-    if (ru == 0) return j == 0 ? 0 : a;
-    if (j == 0) return b;
-    return inner(a, b, d, m);
-}
 // the same pixel of the band before: its value px and its neighbours pa, pb, pd (unused by the plain modes)
 P3_HD int predict_mode(int ru, int j, int a, int b, int d, int px, int pa, int pb, int pd, int mode)
 {
@@ -96,125 +78,6 @@ P3_HD int predict_mode(int ru, int j, int a, int b, int d, int px, int pa, int p
     int p = predict(ru, j, a, b, d, m);
     if (mode >= NSPATIAL) p += px - predict(ru, j, pa, pb, pd, m);
     return p;
-}
-P3_HD uint32_t fold(int x, int pred)
-{
-    const int e = (int)(short)(unsigned short)(x - pred);
-    return e >= 0 ? 2u * (uint32_t)e : (uint32_t)(-2 * e - 1);
-}
-P3_HD int unfold(uint32_t v) { return (v & 1u) ? -(int)((v + 1u) >> 1) : (int)(v >> 1); }
-
-// ---------------------------------------------------------------- the lane coder
-
-struct Lane {
-    uint32_t A, N;
-    int left;
-    bool zero;
-    P3_HD void init(int k0, int z0)
-    {
-        N = 4;
-        A = z0 == 2 ? 0u : (z0 == 1 ? 1u : 6u << k0);
-        left = 0;
-        zero = false;
-    }
-    P3_HD void row() { left = 0; zero = false; }        // groups do not cross rows
-    P3_HD int k() const
-    {
-        int kk = 0;
-        while (kk < 15 && (N << (kk + 1)) < A) ++kk;
-        return kk;
-    }
-    P3_HD int group() const { return 16 * A < N ? 16 : (2 * A < N ? 4 : 1); }
-    P3_HD void update(uint32_t v)
-    {
-        left -= 1;
-        A += v;
-        N += 1;
-        if (N == 32) { A = (A + 1) >> 1; N = 16; }
-    }
-};
-
-P3_HD void start_parameters(uint32_t best, uint32_t count, int* k0, int* z0)
-{
-    int k = 0;
-    while (k < 15 && ((uint64_t)count << (k + 1)) < best) ++k;
-    *k0 = k;
-    *z0 = 16ull * best < count ? 2 : (2ull * best < count ? 1 : 0);
-}
-P3_HD uint32_t head_word(int k0, int z0) { return (uint32_t)k0 | ((uint32_t)z0 << 12); }
-P3_HD bool read_head_word(uint32_t w, int* k0, int* z0)
-{
-    *k0 = (int)(w & 0xFFu); *z0 = (int)(w >> 12);
-    if (*k0 > 15 || *z0 > 2 || (w & 0xF00u)) { *k0 = 0; *z0 = 0; return false; }
-    return true;
-}
-
-// Sample j of a row of tw folded residuals v[0 .. tw): its bits (at most 32, right-aligned in *code) and their number;
-// advances the lane's state.
-P3_HD int encode_symbol(Lane& st, const uint16_t* v, int j, int tw, uint32_t* code_out)
-{
-    uint32_t code = 0;
-    int len = 0;
-    if (st.left == 0) {
-        int gsz = st.group();
-        st.zero = false;
-        if (gsz > 1) {
-            gsz = gsz < tw - j ? gsz : tw - j;
-            bool all0 = true;
-            for (int u = 0; u < gsz; ++u) all0 = all0 && v[j + u] == 0;
-            code = all0 ? 0u : 1u;
-            len = 1;
-            st.zero = all0;
-        }
-        st.left = gsz;
-    }
-    const uint32_t x = v[j];
-    if (!st.zero) {
-        const int kk = st.k();
-        const uint32_t q = x >> kk;
-        if (q < (uint32_t)QESC) {
-            code = (code << (q + 1 + kk)) | (((1u << q) - 1u) << (kk + 1)) | (x & ((1u << kk) - 1u));
-            len += (int)q + 1 + kk;
-        } else {
-            code = (code << 31) | (0x7FFFu << 16) | x;
-            len += 31;
-        }
-    }
-    st.update(x);
-    *code_out = code;
-    return len;
-}
-
-P3_HD int leading_ones(uint32_t top)
-{
-    const uint32_t inv = ~top;
-    return inv ? __builtin_clz(inv) : 32;
-}
-// The inverse: top holds the lane's next 32 unread bits, MSB first.  Returns the folded residual, *len the bits it took.
-P3_HD uint32_t decode_symbol(Lane& st, uint32_t top, int j, int tw, int* len_out)
-{
-    uint32_t v = 0;
-    int len = 0;
-    if (st.left == 0) {
-        int gsz = st.group();
-        st.zero = false;
-        if (gsz > 1) {
-            gsz = gsz < tw - j ? gsz : tw - j;
-            st.zero = !(top >> 31);
-            top <<= 1;
-            len = 1;
-        }
-        st.left = gsz;
-    }
-    if (!st.zero) {
-        const int kk = st.k();
-        int q = leading_ones(top);
-        if (q >= QESC) { v = (top >> 1) & 0xFFFFu; len += 31; }
-        else { v = ((uint32_t)q << kk) | ((top >> (31 - q - kk)) & ((1u << kk) - 1u)); len += q + 1 + kk; }
-    }
-    st.update(v);
-    *len_out = len;
-    return v;
 }
 
 // ---------------------------------------------------------------- mode words

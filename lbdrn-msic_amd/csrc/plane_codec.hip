@@ -17,6 +17,10 @@
 // predictor's left / up / up-left neighbours become available), so decoding is one coalesced word stream per
 // wave, the per-step hand-out is a ballot + mbcnt, and no lane ever waits for another lane's bits.
 //
+// The predictors, the fold and the lane coder are plane_lane.inc, and the bit writer, the replay and the hand-out are
+// plane_wave.hpp: one text each, which LBB3 (plane3.hip) is built from as well.  What is here is LBB2's own: the strip,
+// one mode word per pass, the lane's coder state in registers over the strip's passes.
+//
 // Encoder, per strip (one 64-thread workgroup): phase A walks the passes -- stage the 65 x 64 pixel window in
 // LDS, residual sums of the four predictors (wave reduction), code the lane's row into its private stream
 // (global scratch) and record each symbol's length; phase B replays the decoder's requests from the recorded
@@ -28,12 +32,13 @@
 #include <rocprim/rocprim.hpp>
 
 #include "common.hpp"
+#include "plane_lane.inc"
+#include "plane_wave.hpp"
 
 namespace lbdrn {
 
-constexpr int PL_T = 64;      // strip width = lanes = rows per pass
-constexpr int PL_NMODES = 4;
-constexpr int PL_QESC = 15;   // unary length that announces a raw 16-bit value
+constexpr int PL_T = plane_lane::T;      // strip width = lanes = rows per pass
+constexpr int PL_NMODES = plane_lane::NSPATIAL;
 
 struct PlaneGeom {
     int C, H, W, TX, NP;
@@ -84,69 +89,6 @@ static int carve_plane(const PlaneGeom& g, void* ws, PlaneWs* w)
     return 0;
 }
 
-// ------------------------------------------------------------------ the symbol coder (both directions)
-
-__device__ __forceinline__ int pl_inner(int a, int b, int c, int mode)
-{
-    if (mode == 0) {
-        const int mn = min(a, b), mx = max(a, b);
-        return c >= mx ? mn : (c <= mn ? mx : a + b - c);
-    }
-    if (mode == 1) return (a + b) >> 1;
-    if (mode == 2) return a + b - c;
-    return ((3 * (a + b) - 2 * c + (1 << 20)) >> 2) - (1 << 18);
-}
-// r: row in the image, j: column in the strip; a left, b up, c up-left
-__device__ __forceinline__ int pl_predict(int r, int j, int a, int b, int c, int mode)
-{
-    if (r == 0) return j == 0 ? 0 : a;
-    if (j == 0) return b;
-    return pl_inner(a, b, c, mode);
-}
-__device__ __forceinline__ uint32_t pl_fold(int x, int pred)
-{
-    const int e = (int)(short)(unsigned short)(x - pred);
-    return e >= 0 ? 2u * (uint32_t)e : (uint32_t)(-2 * e - 1);
-}
-
-struct LaneCoder {
-    uint32_t A, N;
-    int left;
-    bool zero;
-    __device__ void init(int k0, int z0)
-    {
-        N = 4;
-        A = z0 == 2 ? 0u : (z0 == 1 ? 1u : 6u << k0);
-        left = 0;
-        zero = false;
-    }
-    __device__ int k() const
-    {
-        int kk = 0;
-        while (kk < 15 && (N << (kk + 1)) < A) ++kk;
-        return kk;
-    }
-    __device__ int group() const { return 16 * A < N ? 16 : (2 * A < N ? 4 : 1); }
-    __device__ void update(uint32_t v)
-    {
-        left -= 1;
-        A += v;
-        N += 1;
-        if (N == 32) { A = (A + 1) >> 1; N = 16; }
-    }
-};
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int lanes_below(unsigned long long mask)
-{
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // ------------------------------------------------------------------ encoder
 
 __global__ void __launch_bounds__(PL_T) k_plane_encode(const uint16_t* __restrict__ planes, PlaneGeom g, PlaneWs w,
@@ -167,12 +109,10 @@ __global__ void __launch_bounds__(PL_T) k_plane_encode(const uint16_t* __restric
     uint32_t* wout = w.words + (size_t)strip * g.capw;
 
     // ---- phase A: private streams
-    LaneCoder st;
+    plane_lane::Lane st;
     st.init(0, 0);
     int k0 = 0, z0 = 0;
-    unsigned long long acc = 0;
-    int nb = 0;
-    size_t pwords = 0;
+    BitWriter bits;
     for (int p = 0; p < g.NP; ++p) {
         const int rows = min(PL_T, g.H - p * PL_T);
         __syncthreads();
@@ -186,7 +126,7 @@ __global__ void __launch_bounds__(PL_T) k_plane_encode(const uint16_t* __restric
                 const int a = j ? px[lane + 1][j - 1] : 0, b = r ? px[lane][j] : 0, cc = (j && r) ? px[lane][j - 1] : 0;
                 const int x = px[lane + 1][j];
 #pragma unroll
-                for (int m = 0; m < PL_NMODES; ++m) sum[m] += pl_fold(x, pl_predict(r, j, a, b, cc, m));
+                for (int m = 0; m < PL_NMODES; ++m) sum[m] += plane_lane::fold(x, plane_lane::predict(r, j, a, b, cc, m));
             }
         int mode = 0;
         uint32_t best = wave_sum(sum[0]);
@@ -197,102 +137,40 @@ __global__ void __launch_bounds__(PL_T) k_plane_encode(const uint16_t* __restric
         }
         if (lane == 0) gmodes[p] = mode;
         if (p == 0) {
-            const unsigned long long count = (unsigned long long)rows * tw;
-            while (k0 < 15 && (count << (k0 + 1)) < best) ++k0;
-            z0 = 16ull * best < count ? 2 : (2ull * best < count ? 1 : 0);
+            plane_lane::start_parameters(best, (uint32_t)(rows * tw), &k0, &z0);
             st.init(k0, z0);
         }
         if (lane < rows) {
             for (int j = 0; j < tw; ++j) {
                 const int a = j ? px[lane + 1][j - 1] : 0, b = r ? px[lane][j] : 0, cc = (j && r) ? px[lane][j - 1] : 0;
-                vrow[lane][j] = (uint16_t)pl_fold(px[lane + 1][j], pl_predict(r, j, a, b, cc, mode));
+                vrow[lane][j] = (uint16_t)plane_lane::fold(px[lane + 1][j], plane_lane::predict(r, j, a, b, cc, mode));
             }
-            st.left = 0;  // groups do not cross rows
+            st.row();
             for (int j = 0; j < tw; ++j) {
-                const uint32_t v = vrow[lane][j];
-                uint32_t code = 0;
-                int len = 0;
-                if (st.left == 0) {
-                    int gsz = st.group();
-                    st.zero = false;
-                    if (gsz > 1) {
-                        gsz = min(gsz, tw - j);
-                        bool all0 = true;
-                        for (int u = 0; u < gsz; ++u) all0 = all0 && vrow[lane][j + u] == 0;
-                        code = all0 ? 0u : 1u;
-                        len = 1;
-                        st.zero = all0;
-                    }
-                    st.left = gsz;
-                }
-                if (!st.zero) {
-                    const int kk = st.k();
-                    const uint32_t q = v >> kk;
-                    if (q < (uint32_t)PL_QESC) {
-                        code = (code << (q + 1 + kk)) | (((1u << q) - 1u) << (kk + 1)) | (v & ((1u << kk) - 1u));
-                        len += (int)q + 1 + kk;
-                    } else {
-                        code = (code << 31) | (0x7FFFu << 16) | v;
-                        len += 31;
-                    }
-                }
+                uint32_t code;
+                const int len = plane_lane::encode_symbol(st, &vrow[lane][0], j, tw, &code);
                 lensw[lane][j] = (uint8_t)len;
-                if (len) {
-                    acc = (acc << len) | code;
-                    nb += len;
-                    if (nb >= 32) {
-                        priv[pwords++] = (uint32_t)(acc >> (nb - 32));
-                        nb -= 32;
-                    }
-                }
-                st.update(v);
+                bits.put(priv, code, len);
             }
         }
         __syncthreads();
-        {   // the pass's symbol lengths, 4 KB, coalesced
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(&lensw[0][0]);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(glens + (size_t)p * PL_T * PL_T);
-            for (int idx = lane; idx < PL_T * PL_T / 4; idx += PL_T) dst[idx] = src[idx];
-        }
+        copy_lens_tile(glens + (size_t)p * PL_T * PL_T, &lensw[0][0], lane);
     }
-    if (lane < g.H) priv[pwords++] = nb ? (uint32_t)(acc << (32 - nb)) : 0u;  // tail, zero padded
+    if (lane < g.H) bits.tail(priv);
     __threadfence_block();
     __syncthreads();
 
     // ---- phase B: the decoder's request order
-    uint32_t nw = 0;
-    if (lane == 0) wout[0] = (uint32_t)k0 | ((uint32_t)z0 << 12);
-    nw = 1;
-    int fill = 0;
-    size_t taken = 0;
+    if (lane == 0) wout[0] = plane_lane::head_word(k0, z0);
+    Replay rp;
+    rp.nw = 1;
     for (int p = 0; p < g.NP; ++p) {
         const int rows = min(PL_T, g.H - p * PL_T);
-        if (lane == 0) wout[nw] = (uint32_t)gmodes[p];
-        nw += 1;
-        __syncthreads();
-        {
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(glens + (size_t)p * PL_T * PL_T);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(&lensw[0][0]);
-            for (int idx = lane; idx < PL_T * PL_T / 4; idx += PL_T) dst[idx] = src[idx];
-        }
-        const size_t taken0 = taken;
-        for (int u = 0; u <= PL_T; ++u) pwin[lane][u] = taken0 + u < pwords ? priv[taken0 + u] : 0u;
-        __syncthreads();
-        for (int d = 0; d < rows + tw - 1; ++d) {
-            const int j = d - lane;
-            const bool active = lane < rows && j >= 0 && j < tw;
-            const bool need = active && fill < 32;
-            const unsigned long long mask = __ballot(need);
-            if (need) {
-                wout[nw + lanes_below(mask)] = pwin[lane][taken - taken0];
-                taken += 1;
-                fill += 32;
-            }
-            nw += (uint32_t)__popcll(mask);
-            if (active) fill -= lensw[lane][j];
-        }
+        if (lane == 0) wout[rp.nw] = (uint32_t)gmodes[p];
+        rp.nw += 1;
+        rp.band(glens + (size_t)p * PL_T * PL_T, priv, bits.pwords, rows, tw, lane, lensw, pwin, wout);
     }
-    if (lane == 0) counts[strip] = nw;
+    if (lane == 0) counts[strip] = rp.nw;
 }
 
 __global__ void __launch_bounds__(256) k_plane_compact(const uint32_t* __restrict__ strips, size_t capw,
@@ -330,64 +208,33 @@ __global__ void __launch_bounds__(PL_T) k_plane_decode(const uint32_t* __restric
     bool bad = false;
     if (off + nws > total_words) { nws = 0; bad = true; }   // counts that overrun the payload
     const uint32_t* ws = words + off;
-    const uint32_t w0 = nws ? ws[0] : 0u;
-    int k0 = (int)(w0 & 0xFF), z0 = (int)(w0 >> 12);
-    if (nws < 1 || k0 > 15 || z0 > 2 || (w0 & 0xF00)) { bad = true; k0 = 0; z0 = 0; }
-    LaneCoder st;
+    int k0, z0;
+    if (nws < 1 || !plane_lane::read_head_word(ws[0], &k0, &z0)) { bad = true; k0 = 0; z0 = 0; }
+    plane_lane::Lane st;
     st.init(k0, z0);
-    unsigned long long buf = 0;
-    int nb = 0;
-    uint32_t cur = 1;
+    WordReader rd;
+    rd.cur = 1;
     for (int p = 0; p < g.NP; ++p) {
         const int rows = min(PL_T, g.H - p * PL_T);
         int mode = 0;
-        if (cur < nws) mode = (int)ws[cur]; else bad = true;
+        if (rd.cur < nws) mode = (int)ws[rd.cur]; else bad = true;
         if (mode < 0 || mode >= PL_NMODES) { bad = true; mode = 0; }
-        cur += 1;
-        const uint32_t cur0 = cur;
+        rd.cur += 1;
         __syncthreads();
-        for (int idx = lane; idx < PL_WWIN; idx += PL_T) wwin[idx] = (uint64_t)cur0 + idx < nws ? ws[cur0 + idx] : 0u;
+        rd.stage(wwin, PL_WWIN, ws, nws, lane);
         __syncthreads();
-        st.left = 0;
+        st.row();
         const int r = p * PL_T + lane;
         for (int d = 0; d < rows + tw - 1; ++d) {
             const int j = d - lane;
             const bool active = lane < rows && j >= 0 && j < tw;
-            const bool need = active && nb < 32;
-            const unsigned long long mask = __ballot(need);
-            if (need) {
-                const uint32_t idx = cur + (uint32_t)lanes_below(mask);
-                if (idx >= nws) bad = true;
-                buf |= (unsigned long long)wwin[min(idx - cur0, (uint32_t)PL_WWIN - 1)] << (32 - nb);
-                nb += 32;
-            }
-            cur += (uint32_t)__popcll(mask);
+            if (!rd.refill(active, wwin, PL_WWIN, nws)) bad = true;
             if (active) {
-                uint32_t top = (uint32_t)(buf >> 32), v = 0;
-                int len = 0;
-                if (st.left == 0) {
-                    int gsz = st.group();
-                    st.zero = false;
-                    if (gsz > 1) {
-                        gsz = min(gsz, tw - j);
-                        st.zero = !(top >> 31);
-                        top <<= 1;
-                        len = 1;
-                    }
-                    st.left = gsz;
-                }
-                if (!st.zero) {
-                    const int kk = st.k();
-                    const int q = min(__clz((int)~top), PL_QESC);   // leading ones, at most the escape length
-                    if (q >= PL_QESC) { v = (top >> 1) & 0xFFFFu; len += 31; }
-                    else { v = ((uint32_t)q << kk) | ((top >> (31 - q - kk)) & ((1u << kk) - 1u)); len += q + 1 + kk; }
-                }
-                buf <<= len;
-                nb -= len;
-                st.update(v);
-                const int e = (v & 1u) ? -(int)((v + 1u) >> 1) : (int)(v >> 1);
+                int len;
+                const uint32_t v = plane_lane::decode_symbol(st, rd.top(), j, tw, &len);
+                rd.drop(len);
                 const int a = j ? px[lane + 1][j - 1] : 0, b = r ? px[lane][j] : 0, cc = (j && r) ? px[lane][j - 1] : 0;
-                px[lane + 1][j] = (uint16_t)(pl_predict(r, j, a, b, cc, mode) + e);
+                px[lane + 1][j] = (uint16_t)(plane_lane::predict(r, j, a, b, cc, mode) + plane_lane::unfold(v));
             }
             __syncthreads();   // one wave: orders this step's LDS write before the neighbours' reads of the next
         }
@@ -396,7 +243,7 @@ __global__ void __launch_bounds__(PL_T) k_plane_decode(const uint32_t* __restric
         if (lane < tw) px[0][lane] = px[PL_T][lane];   // the next pass's row above (unused after a short pass)
         __syncthreads();
     }
-    if (cur != nws) bad = true;
+    if (rd.cur != nws) bad = true;
     if (bad) atomicOr(status, 1);
 }
 

@@ -1,10 +1,11 @@
 """LBB3, the MSB payload with inter-band prediction, on the GPU: the kernels of csrc/plane3.hip against the sequential
-restatement tests/plane3_reference.py -- byte identity both ways and the round trip on the shared case list; repeatability;
+restatement tests/plane3_reference.py -- byte identity both ways and the round trip on the shared case list; LBB2's body from both libraries where the two formats coincide; repeatability;
 guarded, pre-filled buffers; a capacity one byte short; the fixed list of damaged units; encode.py / decode.py under
 LBDRN_BASE_CODEC=LBB3 against the default; and the sharded launch, sweep.py and LBDRN_REPORT_BOTH_BPSP under it."""
 import contextlib
 import ctypes
 import os
+import struct
 import sys
 
 import numpy as np
@@ -45,6 +46,32 @@ def test_reader_takes_other_unit_heights(dev, S):
         body = R.case_body(name, x, S)
         assert plane3.info(body) == x.shape + (S,)
         assert np.array_equal(ops.from_device_u16(plane3.decode(body, *x.shape, dev)), x)
+
+
+def _one_band_cases():
+    """the smallest one-band shapes that reach the partial last strip (tw < 64), the short last pass (rows < 64), the carried row
+    above (H > 64), the zero-group states (z0 = 2) and the 31-bit escape; H <= 256, the writer's S"""
+    rng = np.random.default_rng(0)
+    yield "one pixel", np.array([[[513]]], np.uint16)
+    yield "one row", rng.integers(0, 300, (1, 1, 257)).astype(np.uint16)
+    yield "one column", rng.integers(0, 300, (1, 130, 1)).astype(np.uint16)
+    yield "constant", np.full((1, 65, 64), 40000, np.uint16)
+    yield "noise 16 bit", rng.integers(0, 65536, (1, 129, 67)).astype(np.uint16)
+    yield "sparse spikes", ((rng.random((1, 200, 130)) < 0.02) * rng.integers(0, 65536, (1, 200, 130))).astype(np.uint16)
+    yield "zeros", np.zeros((1, 70, 90), np.uint16)
+
+
+@pytest.mark.parametrize("name,x", list(_one_band_cases()), ids=[n for n, _ in _one_band_cases()])
+def test_one_band_in_one_row_of_units_is_the_lbb2_body(dev, name, x):
+    """The two libraries are built from one lane coder and one wave walk: where the formats coincide -- one band, no unit
+    boundary inside the height -- liblbdrn_plane3.so writes liblbdrn_hip.so's LBB2 body behind its header, and reads it."""
+    _, H, W = x.shape
+    assert H <= R.WRITER_S
+    x_d = ops.to_device_u16(x, dev)
+    lbb2 = ops.plane_encode(x_d)
+    assert plane3.encode(x_d)[4 * R.HEADER_WORDS:] == lbb2
+    back = plane3.decode(R.MAGIC + struct.pack("<4I", 1, H, W, R.WRITER_S) + lbb2, 1, H, W, dev)      # (raises unless the status is 0)
+    assert np.array_equal(ops.from_device_u16(back), x)
 
 
 def test_two_encodes_give_the_same_bytes(dev):

@@ -142,6 +142,9 @@ def test_dependency_rule_is_no_narrower_than_the_hand_written_lists():
         # and one library's own text is not another's: the main library does not wait for plane3.inc
         if lib["stem"] != "plane3":
             assert os.path.join(CSRC, "plane3.inc") not in got, lib["stem"]
+        # the lane coder and the wave walk are one text for LBB2 (the main library) and LBB3, and nobody else's
+        for shared in ("plane_lane.inc", "plane_wave.hpp"):
+            assert (os.path.join(CSRC, shared) in got) == (lib["stem"] in ("hip", "plane3")), (lib["stem"], shared)
         includes = [f for f in got if open(f, errors="replace").read().count('#include "error_buffer.inc"')]
         assert len(includes) == 1, (lib["stem"], includes)      # one message buffer per library
 
@@ -194,3 +197,16 @@ def test_the_copies_are_gone():
         mod = importlib.import_module("lbdrn_hip." + name)
         assert (mod.E_ARG, mod.E_DEVICE, mod.E_UNSUPPORTED, mod.E_WORKSPACE) == (-1, -2, -3, -4)
         assert mod.lib == mod._NATIVE.lib and mod.available == mod._NATIVE.available and mod._PATH == mod._NATIVE.path and callable(mod._check)
+
+
+def test_the_plane_coders_share_one_text():
+    """LBB2 and LBB3 are one lane coder (csrc/plane_lane.inc) and one wave walk (csrc/plane_wave.hpp): the adaptive-k loop, the
+    escape code and the ballot's mbcnt stand in one file each, and plane_codec.hip has no coder of its own"""
+    texts = {f: open(os.path.join(CSRC, f)).read() for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".inc", ".hpp"))}
+    assert [f for f, t in texts.items() if "(N << (kk + 1)) < A" in t] == ["plane_lane.inc"]
+    assert [f for f, t in texts.items() if "0x7FFFu << 16" in t] == ["plane_lane.inc"]
+    assert [f for f, t in texts.items() if f.startswith("plane") and "mbcnt_hi" in t] == ["plane_wave.hpp"]
+    assert sorted(f for f in texts if f.startswith("plane")) == ["plane3.hip", "plane3.inc", "plane_codec.hip", "plane_lane.inc", "plane_wave.hpp"]
+    for gone in ("pl_inner", "pl_fold", "LaneCoder"):
+        assert gone not in texts["plane_codec.hip"], gone
+    assert '#include "plane3.inc"' not in texts["plane_codec.hip"]

@@ -1,6 +1,7 @@
 """LBB3 on the CPU: tests/plane3_reference.py (the format restated from include/lbdrn_plane3.h) round-trips itself; the host
 build of csrc/plane3.inc -- through tests/plane3_host_shim.cpp, compiled by g++ into a temporary directory -- writes the same
-bytes and each reads the other's; the rate against LBB2 on a scene whose bands share their structure and on one whose bands
+bytes and each reads the other's; for one band in units as high as the raster it writes LBB2's bytes, by oracle/plane_codec.c
+(the lane coder, csrc/plane_lane.inc, is one text for both formats); the rate against LBB2 on a scene whose bands share their structure and on one whose bands
 do not; lbdrn_plane3_info refuses damaged tables; the container dispatches on the tag; and tests/plane3_damage_main.cpp, a
 stand-alone program built with AddressSanitizer and UndefinedBehaviorSanitizer, feeds the host decoder damaged bodies.
 No GPU.  Every comparison is exact."""
@@ -129,6 +130,52 @@ def test_other_unit_heights(shim, S):
         assert rc == 0 and np.array_equal(back, x)
     x = dict(CASES)["2x65x64"]
     assert np.array_equal(R.decode(shim_encode(shim, x, S)), x)
+
+
+# ---------------------------------------------------------------- one lane coder: where the two formats coincide
+
+def _lbb2_cases():
+    from test_gpu_plane_codec import _cases      # LBB2's own case list (the module needs no GPU to import)
+    return list(_cases())
+
+
+LBB2_CASES = _lbb2_cases()
+
+
+def _lbb2_strips(x):
+    """the oracle's LBB2 body of x: the counts of all strips and then the strips, band-major -> [(count, words)] per strip"""
+    import oracle as O
+    counts, words = O.plane_encode(np.ascontiguousarray(x, np.uint16))
+    ends = np.cumsum(counts.astype(np.int64))
+    assert ends[-1] == words.size
+    return [(counts[i], words[ends[i] - counts[i]:ends[i]]) for i in range(counts.size)]
+
+
+def _lbb2_body(strips):
+    return np.array([n for n, _ in strips], "<u4").tobytes() + b"".join(w.astype("<u4").tobytes() for _, w in strips)
+
+
+@pytest.mark.parametrize("name,x", LBB2_CASES, ids=[n for n, _ in LBB2_CASES])
+def test_shared_text_writes_lbb2_bytes(shim, name, x):
+    """One band in units as high as the raster (S >= H): a unit is LBB2's strip, its head word and its one mode word a pass are
+    LBB2's, and the body behind LBB3's 5-word header is LBB2's body byte for byte -- by oracle/plane_codec.c, which shares no
+    text with csrc/plane_lane.inc."""
+    x = x[:1]
+    _, H, W = x.shape
+    S = 64 * -(-H // 64)
+    want = _lbb2_body(_lbb2_strips(x))
+    assert shim_encode(shim, x, S)[4 * R.HEADER_WORDS:] == want
+    rc, back = shim_decode(shim, R.MAGIC + struct.pack("<4I", 1, H, W, S) + want, 1, H, W, S)
+    assert rc == 0 and np.array_equal(back, x)
+
+
+def test_each_band_alone_is_its_strips_of_the_lbb2_body(shim):
+    name, x = LBB2_CASES[7]
+    assert name == "noise 8 bit" and x.shape == (3, 64, 64)
+    strips = _lbb2_strips(x)
+    assert len(strips) == 3      # one strip a band, band-major
+    for c in range(3):
+        assert shim_encode(shim, x[c:c + 1], 64)[4 * R.HEADER_WORDS:] == _lbb2_body(strips[c:c + 1]), c
 
 
 # ---------------------------------------------------------------- rate
