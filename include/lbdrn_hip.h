@@ -20,6 +20,24 @@
  *  - images are channel-planar [C][H][W] uint16, as GDAL's ReadAsArray() returns them
  *    (ref LBDRNdataset.py:93-94); feature / label matrices are row-major [N][F] / [N][C]
  *    float32, row n = pixel y*W+x (ref LBDRNdataset.py:129-131).
+ *
+ * Alignment.  Every pointer argument has a minimum alignment; a non-NULL pointer below it returns LBDRN_E_ARG with the
+ * argument's name in lbdrn_last_error(), before the device is looked for and before anything is launched or read.  Arrays
+ * need no more than the rule says: a view into a larger buffer (one band of a cube, one row of a stack of parameter
+ * vectors, a slice of a permutation) is a valid argument where its first byte satisfies it.
+ *    2-byte aligned    uint16 rasters: img, msb, out, planes
+ *    4-byte aligned    float32 arrays: params (but see below), x, t, y, dy, dx, grads, y_out, labels, features, exp_avg,
+ *                      exp_avg_sq, loss, losses, g->rowtab, g->coltab; the int32 words msb_max and status; the LBB2 body
+ *                      (read and written as 32-bit words); on the host: values of the weight payload calls
+ *    8-byte aligned    int64 indices: idx, perm (lbdrn_train_epoch, _group and lbdrn_randperm's output); the float64 sum sse;
+ *                      the uint64 word body_bytes
+ *    16-byte aligned   params of lbdrn_train_epoch and of every fit of lbdrn_train_epoch_group, on any path: the fused
+ *                      training steps read the bias vectors sixteen bytes at a time.  (exp_avg and exp_avg_sq: 4.)
+ *    256-byte aligned  every workspace and the tape: the library lays its regions out at multiples of 256 from the base
+ *                      and reads them as wide as a region's type allows
+ * The arrays of pointers of lbdrn_train_epoch_group, the seeds of lbdrn_randperm, the two structs and the byte streams of
+ * the weight payload and lbdrn_jp2k_encode's `out` are host memory read or written bytewise or as what their C type says:
+ * nothing beyond what a C compiler gives them.
  */
 #ifndef LBDRN_HIP_H
 #define LBDRN_HIP_H
@@ -92,17 +110,20 @@ int32_t lbdrn_feature_dim(const lbdrn_geom *g);
 
 /* a1 -- LBDRNdataset.py:95-101: msb = img >> K (uint16 plane, same layout) and the running
  * maximum of msb into *msb_max (device int32, must be zeroed by the caller or hold a previous
- * maximum).  msb may be NULL (max only). */
+ * maximum).  msb may be NULL (max only).  *msb_max is only ever RAISED (an atomic integer maximum): a value above the
+ * plane's maximum stays, one below it becomes the plane's maximum. */
 int lbdrn_split_bits(const uint16_t *img, int32_t C, int32_t H, int32_t W, int32_t K,
                      uint16_t *msb, int32_t *msb_max, void *stream);
 
 /* a1 -- LBDRNdataset.py:96-97,131: labels[i][c] = float(img - (msb<<K)) / (2^K-1) for the pixels
- * idx[0..n) (int64 device indices) or, when idx is NULL, for pixels 0..n-1 in raster order. */
+ * idx[0..n) (int64 device indices) or, when idx is NULL, for pixels 0..n-1 in raster order.
+ * An idx entry outside [0, H*W) is CLAMPED into it (a negative one reads pixel 0, one at or beyond H*W pixel H*W-1), here
+ * and in lbdrn_features: no entry makes either call read outside the raster. */
 int lbdrn_labels(const uint16_t *img, int32_t C, int32_t H, int32_t W, int32_t K,
                  const int64_t *idx, int64_t n, float *labels, void *stream);
 
 /* a2/a3 -- LBDRNdataset.py:104-130 (dup. decode.py:77-102): feature rows for idx[0..n) or raster
- * order.  msb is the [C][H][W] uint16 MSB plane. */
+ * order.  msb is the [C][H][W] uint16 MSB plane.  idx entries outside [0, H*W) are clamped as in lbdrn_labels. */
 int lbdrn_features(const lbdrn_geom *g, const uint16_t *msb, const int64_t *idx, int64_t n,
                    float *features, void *stream);
 
@@ -148,6 +169,7 @@ int lbdrn_decode_fused(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t
 /* a9 -- evaluator + LBDRNPerformance (modified_ignite_engine.py:38-43, LBDRNperformance.py:18-21):
  * *sse (device float64) = sum over all pixels and bands of (y - label)^2, fixed summation order
  * (bitwise reproducible, on any launch shape).  img is the original [C][H][W] image the labels derive from.
+ * *sse is OVERWRITTEN on every path: what it held on entry does not matter, and sums over several calls are the caller's.
  * path may carry LBDRN_EVAL_BACKGROUND (path | LBDRN_EVAL_BACKGROUND): the pass is launched on half as many
  * workgroups, for running on a second stream beside a fit's training steps (which hold the other half of the CUs).
  * Same *sse bit for bit. */
@@ -160,8 +182,16 @@ int lbdrn_decode_fused(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t
  * the pass 20 % shorter.  Still a fixed summation order: bitwise reproducible, same sum on any launch shape.  The
  * generic path ignores the flag.
  * With the flag the fused kernels take the colour window from img >> g->K and DO NOT READ msb (one plane read per pass
- * instead of two): msb must be exactly that plane -- as lbdrn_split_bits leaves it -- or NULL.  A caller whose MSB plane is
- * something else (a decoded or modified base) must leave the flag out. */
+ * instead of two): msb must be exactly that plane -- as lbdrn_split_bits leaves it.  A caller whose MSB plane is
+ * something else (a decoded or modified base) must leave the flag out.
+ * msb may be NULL only where a fast instance of the fused kernels serves the call, which is decided on the host before
+ * anything is launched: the flag is set, the path is not LBDRN_PATH_GENERIC, the shape has a fused apply kernel, and the
+ * instance of it that serves the shape is a fast one -- bc = 32 or 64 with at most 8 bands (the kernel that keeps the
+ * weights in LDS), or the streaming kernel (bc = 256, and bc = 128 where the weights do not fit in LDS).  Everywhere else
+ * something reads msb and a NULL returns LBDRN_E_ARG: without the flag, on the generic path (chosen, or taken by
+ * LBDRN_PATH_AUTO for a shape without a fused kernel), and for a fast request that a canonical instance serves -- more
+ * than 8 bands at bc = 32 or 64 (for instance C = 10, bc = 64), or bc = 128 with the weights in LDS.  A caller that does
+ * not want to restate this passes the plane: it is never wrong to. */
 #define LBDRN_EVAL_FAST 0x400
 /* With LBDRN_EVAL_FAST, path may also carry LBDRN_EVAL_X16 (round 6; OPT-IN: no caller of this package sets it by default): the
  * colour features of layer 0 run on the f16 matrix pipe with EXACT operands.  A relative colour feature is
@@ -182,8 +212,14 @@ int lbdrn_eval_sse(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t *im
  * params/exp_avg/exp_avg_sq in place.  adam_step0 = number of Adam steps already taken;
  * losses (optional) receives one float32 minibatch loss per step.  The last minibatch may be
  * short (no drop_last, encode.py:69) -- down to ONE row; no byte of perm beyond its n elements is read.
- * batch_size: any value >= 1 (the reference takes any -bs).  The fused bc = 64 step addresses one step's gradient slabs
- * with 32-bit offsets: where they would pass 2 GiB (about 0.9 million rows per minibatch at the headline shape)
+ * perm: every entry must lie in [0, H*W).  Unlike lbdrn_labels and lbdrn_features, the training calls promise nothing for
+ * an entry outside the raster (some steps clamp it, none is required to): a permutation of the pixels, or any list of
+ * valid pixel indices -- n may exceed H*W --, is the contract.
+ * batch_size: any value >= 1 (the reference takes any -bs), up to INT32_MAX: the workspace arithmetic is done in size_t and
+ * does not wrap.  lbdrn_train_workspace sizes a step for batch_size rows WHATEVER the raster holds -- lbdrn_train_step's
+ * workspace is asked for through it with a one-pixel geometry --, so a caller whose -bs exceeds its n passes min(bs, n):
+ * the same single minibatch, the same numbers, and a workspace for the rows there are.
+ * The fused bc = 64 step addresses one step's gradient slabs with 32-bit offsets: where they would pass 2 GiB (about 0.9 million rows per minibatch at the headline shape)
  * LBDRN_PATH_MFMA answers LBDRN_E_UNSUPPORTED and LBDRN_PATH_AUTO runs the generic step (same tolerance contract).
  * Which shapes have a fused step: bc = 64 with one or two hidden layers (Sine or ReLU) and up to 256 multiplied features
  * (lbdrn_train_step_features), three hidden layers (Sine) up to F = 160 (ten 16-wide strips of dW_0: beyond, the tile kernel's
@@ -326,7 +362,8 @@ int lbdrn_weights_info(const void *stream, size_t nbytes, int64_t *n, int32_t *p
 int lbdrn_weights_decode(const void *stream, size_t nbytes, float *values, int64_t capacity);
 
 /* a7/a8 building block exposed for teacher-forced parity tests: one update on an explicit
- * minibatch x[B][F], t[B][C]; grads (optional) receives d(loss)/d(params). */
+ * minibatch x[B][F], t[B][C]; grads (optional) receives d(loss)/d(params).  workspace: lbdrn_train_workspace(g, net, B)
+ * bytes, for any valid geometry g with g->C = net->C (a raster of one pixel will do: only B and the network count). */
 int lbdrn_train_step(const lbdrn_net *net, const float *x, const float *t, int32_t B,
                      float *params, float *exp_avg, float *exp_avg_sq, int64_t adam_step,
                      double lr, int32_t apply_adam, float *loss, float *grads, void *workspace,

@@ -26,6 +26,8 @@
  *   lbdrn_jp2kd_decode     buf is HOST memory (n bytes), planes DEVICE memory [C][H][W] uint16; C, H, W must be the file's.
  *                          The workspace's contents do not matter on entry, nothing beyond workspace_bytes is touched, and
  *                          a workspace shorter than lbdrn_jp2kd_workspace(buf, n) is LBDRN_E_WORKSPACE before any launch.
+ *                          Alignment (LBDRN_E_ARG before any launch otherwise): the workspace 256 bytes (32-bit words from
+ *                          its base), planes 2; buf is read bytewise and needs none.
  *                          Runs on `stream` (a hipStream_t passed as void*; NULL = default stream) and synchronises it.
  */
 #ifndef LBDRN_JP2K_DEC_H

@@ -35,6 +35,9 @@
  * and keeps no state besides that message.  `stream` is a hipStream_t passed as void* (NULL = default stream); the device
  * calls enqueue on it and do not synchronise.  The workspace's contents do not matter on entry, nothing beyond the stated
  * sizes is written, and a short workspace or capacity is LBDRN_E_WORKSPACE before any launch.
+ * Alignment (LBDRN_E_ARG before any launch otherwise): the workspace 256 bytes -- its regions are 32- and 64-bit words at
+ * multiples of 256 from the base --, orig, recon and recon_inout 2, status 4, body_bytes 8.  The body needs none: it is
+ * read and written bytewise.
  *
  *   lbdrn_resid_bound      the most bytes a body of this geometry can take (0: geometry out of range -- C <= 65535,
  *                          H, W <= 2^20)

@@ -19,6 +19,8 @@
  * and keeps no state besides that message.  `stream` is a hipStream_t passed as void* (NULL = default stream); the decode
  * call enqueues on it and does not synchronise.  The workspace's contents do not matter on entry, nothing beyond the
  * stated sizes is written, and a short workspace is LBDRN_E_WORKSPACE before any launch.
+ * Alignment (LBDRN_E_ARG before any launch otherwise): the workspace 256 bytes -- its segment table is 64-bit words at
+ * the base --, status 4, planes of 16-bit samples 2.  The file needs none: it is read bytewise.
  *
  *   lbdrn_tiff_segment_count  segments of the layout; 0: layout out of range (C <= 65535, H, W, seg_w, seg_h <= 2^20,
  *                             bits 8 / 16, a strip layout has seg_w = W and seg_h <= H, at most 2^30 segments)

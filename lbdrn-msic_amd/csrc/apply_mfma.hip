@@ -942,10 +942,20 @@ static int run_pass(Args& A, const ApplyCall& c, int mode, const float* packed, 
     return report_stamps(A, grid, c.s);
 }
 
+// The streaming kernel's plan for a requested mode and the mode of the instance that serves it there; false: the shape has no
+// streaming instance.  Host arithmetic: run_wapply launches what this says, mfma_eval_reads_msb answers from it.
+static bool resolve_wapply(const lbdrn_geom& g, const lbdrn_net& net, int mode, WApplyPlan* plan, int* serving)
+{
+    if (!make_wapply_plan(g, net, plan, mode_fast(mode))) return false;
+    *serving = serving_mode(mode, plan->NT, false);
+    return true;
+}
+
 static int run_wapply(const ApplyCall& c, int mode)
 {
     WApplyArgs A;
-    if (!make_wapply_plan(c.g, c.net, &A.p, mode_fast(mode))) {
+    int serving = mode;
+    if (!resolve_wapply(c.g, c.net, mode, &A.p, &serving)) {
         set_error("shape not supported by the MFMA apply kernels");
         return LBDRN_E_UNSUPPORTED;
     }
@@ -954,14 +964,14 @@ static int run_wapply(const ApplyCall& c, int mode)
     double* partial = (double*)((char*)c.ws + align_up((size_t)A.p.pack_floats * 4, 256));
     k_pack_apply_wide<<<(A.p.pack_floats + 255) / 256, 256, 0, c.s>>>(c.params, c.net, A.p, 2 * c.g.P, packed);
     LBDRN_LAUNCH_CHECK();
-    return run_pass(A, c, serving_mode(mode, A.p.NT, false), packed, partial, dispatch_wapply);
+    return run_pass(A, c, serving, packed, partial, dispatch_wapply);
 }
 
-static int run_apply(const ApplyCall& c, int mode)
+// Which kernel serves a requested mode for this shape, and in which mode: k_apply_mfma on *plan in the mode returned (*wide_mode
+// < 0), or the streaming kernel (apply_wide.inc), to be asked for *wide_mode.  Host arithmetic only: run_apply launches what this
+// says, and mfma_eval_reads_msb answers lbdrn_eval_sse's NULL-msb check from it before anything is launched.
+static int resolve_apply(const lbdrn_geom& g, const lbdrn_net& net, int mode, ApplyPlan* plan, int* wide_mode)
 {
-    const lbdrn_geom& g = c.g;
-    const lbdrn_net& net = c.net;
-    ApplyArgs A;
     if (mode == MODE_EVAL_X16) {   // (a hint: where the x16 weight pack does not fit in LDS, or fits only at a shorter tile than the fast
                                    //  plan's -- C = 8, D = 3, bc = 64 --, the pass is the fast one)
         ApplyPlan fp, xp;
@@ -973,9 +983,36 @@ static int run_apply(const ApplyCall& c, int mode)
     // streaming kernel's or none.  dispatch_apply refuses a fast launch with C > 8 should one ever be asked for.
     const int requested = mode;
     if (mode_fast(mode) && net.C > 8) mode = MODE_EVAL;
-    if (!make_plan(g, net, &A.p, mode_fast(mode), mode == MODE_EVAL_X16))   // too wide for LDS-resident weights: the streaming kernel (apply_wide.inc)
-        return run_wapply(c, requested);
-    mode = serving_mode(mode, A.p.NT, A.p.x16);   // (x16 is a hint: where the shape or the image does not qualify, the pass is the fast one)
+    *wide_mode = -1;
+    if (!make_plan(g, net, plan, mode_fast(mode), mode == MODE_EVAL_X16)) {   // too wide for LDS-resident weights: the streaming kernel
+        *wide_mode = requested;
+        return requested;
+    }
+    return serving_mode(mode, plan->NT, plan->x16);   // (x16 is a hint: where the shape or the image does not qualify, the pass is the fast one)
+}
+
+// lbdrn_hip.h at LBDRN_EVAL_FAST: msb may be NULL exactly where this says false -- the serving instance is a fast one (the
+// colour window comes from img >> K: `mode_fast(MODE) ? A.img ... >> g.K : A.msb ...` in both kernels' staging loops).
+bool mfma_eval_reads_msb(const lbdrn_geom& g, const lbdrn_net& net, bool fast, bool x16)
+{
+    ApplyPlan plan;
+    int wide_mode = -1;
+    int mode = resolve_apply(g, net, fast ? (x16 ? MODE_EVAL_X16 : MODE_EVAL_FAST) : MODE_EVAL, &plan, &wide_mode);
+    if (wide_mode >= 0) {
+        WApplyPlan wp;
+        if (!resolve_wapply(g, net, wide_mode, &wp, &mode)) return true;   // (no fused instance: the call is refused later)
+    }
+    return !mode_fast(mode);
+}
+
+static int run_apply(const ApplyCall& c, int mode)
+{
+    const lbdrn_geom& g = c.g;
+    const lbdrn_net& net = c.net;
+    ApplyArgs A;
+    int wide_mode = -1;
+    mode = resolve_apply(g, net, mode, &A.p, &wide_mode);
+    if (wide_mode >= 0) return run_wapply(c, wide_mode);
     if (int rc = workspace_holds(c, mfma_apply_workspace(g, net))) return rc;
     float* packed = (float*)c.ws;
     const size_t pack_bytes = apply_pack_bytes(g, net);

@@ -23,6 +23,7 @@ int plane_encode(const uint16_t* planes, int C, int H, int W, void* body, size_t
                  void* ws, size_t ws_bytes, hipStream_t s);
 int plane_decode(const void* body, size_t body_bytes, int C, int H, int W, uint16_t* planes, int* status, void* ws,
                  size_t ws_bytes, hipStream_t s);
+int plane_body_aligned(const void* body);
 int64_t mt19937_jump_poly(int segment, uint32_t* out);
 int randperm_batch(const uint64_t* seeds, int count, int64_t n, int64_t* out, void* ws, size_t ws_bytes,
                    hipStream_t s);
@@ -73,6 +74,32 @@ static int device_ok()
         if (int rc_ = device_ok()) return rc_; \
     } while (0)
 
+// The alignment contract of lbdrn_hip.h ("Alignment"), checked on the pointer VALUE: in front of NEED_DEVICE() and of every
+// launch, so a refusal needs no device and dereferences nothing.  A NULL pointer passes (whether an argument may be NULL is
+// its own check).  Data pointers need their element's alignment, workspaces and tapes 256 (every region inside them is
+// carved at a multiple of 256 from the base), the parameter vector of the training epochs 16 (the fused steps read the
+// biases as float4: train_mfma.hip k_train_mfma, train_stream.inc, train_wide.inc).
+static bool aligned_to(const void* p, size_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+// (the message names the ONE argument that is off and its alignment, and carries no address: nothing else in it is a number)
+#define LBDRN_ALIGNED(ptr, a) LBDRN_REQUIRE(aligned_to(ptr, a), #ptr " must be %d-byte aligned (lbdrn_hip.h: Alignment)", (int)(a))
+#define LBDRN_ALIGNED_FIT(arr, f, a) \
+    LBDRN_REQUIRE(aligned_to((arr)[f], a), #arr " of fit %c must be %d-byte aligned (lbdrn_hip.h: Alignment)", (char)('A' + (f)), (int)(a))
+enum { ALIGN_WORKSPACE = 256, ALIGN_TRAIN_PARAMS = 16 };
+
+static int geom_tables_aligned(const lbdrn_geom* g)
+{
+    LBDRN_ALIGNED(g->rowtab, 4);
+    LBDRN_ALIGNED(g->coltab, 4);
+    return 0;
+}
+
+// check_geom for the entry points that go on to launch: the geometry's own pointers too
+static int check_geom_call(const lbdrn_geom* g)
+{
+    if (int rc = check_geom(g)) return rc;
+    return geom_tables_aligned(g);
+}
+
 static int net_matches(const lbdrn_geom* g, const lbdrn_net* net)
 {
     LBDRN_REQUIRE(net->F == feature_dim(*g), "net.F=%d but the geometry yields %d features", net->F,
@@ -117,6 +144,9 @@ int lbdrn_split_bits(const uint16_t* img, int32_t C, int32_t H, int32_t W, int32
 {
     LBDRN_REQUIRE(img && msb_max, "img and msb_max must not be null");
     LBDRN_REQUIRE(C >= 1 && H >= 1 && W >= 1 && K >= 1 && K <= 15, "bad arguments C=%d H=%d W=%d K=%d", C, H, W, K);
+    LBDRN_ALIGNED(img, 2);
+    LBDRN_ALIGNED(msb, 2);
+    LBDRN_ALIGNED(msb_max, 4);
     NEED_DEVICE();
     return generic_split_bits(img, C, H, W, K, msb, msb_max, (hipStream_t)stream);
 }
@@ -127,6 +157,9 @@ int lbdrn_labels(const uint16_t* img, int32_t C, int32_t H, int32_t W, int32_t K
     LBDRN_REQUIRE(img && labels, "img and labels must not be null");
     LBDRN_REQUIRE(C >= 1 && H >= 1 && W >= 1 && K >= 1 && K <= 15 && n >= 0, "bad arguments");
     LBDRN_REQUIRE(idx || n <= (int64_t)H * W, "n exceeds the pixel count");
+    LBDRN_ALIGNED(img, 2);
+    LBDRN_ALIGNED(idx, 8);
+    LBDRN_ALIGNED(labels, 4);
     NEED_DEVICE();
     return generic_labels(img, C, H, W, K, idx, n, labels, (hipStream_t)stream);
 }
@@ -134,9 +167,12 @@ int lbdrn_labels(const uint16_t* img, int32_t C, int32_t H, int32_t W, int32_t K
 int lbdrn_features(const lbdrn_geom* g, const uint16_t* msb, const int64_t* idx, int64_t n,
                    float* features, void* stream)
 {
-    if (int rc = check_geom(g)) return rc;
+    if (int rc = check_geom_call(g)) return rc;
     LBDRN_REQUIRE(msb && features && n >= 0, "msb/features null or n negative");
     LBDRN_REQUIRE(idx || n <= (int64_t)g->H * g->W, "n exceeds the pixel count");
+    LBDRN_ALIGNED(msb, 2);
+    LBDRN_ALIGNED(idx, 8);
+    LBDRN_ALIGNED(features, 4);
     NEED_DEVICE();
     return generic_features(launch_geom(*g), msb, idx, n, 0, features, (hipStream_t)stream);
 }
@@ -152,6 +188,10 @@ int lbdrn_forward(const lbdrn_net* net, const float* params, const float* x, int
 {
     if (int rc = check_net(net)) return rc;
     LBDRN_REQUIRE(params && x && y && B >= 0, "null pointer or negative batch");
+    LBDRN_ALIGNED(params, 4);
+    LBDRN_ALIGNED(x, 4);
+    LBDRN_ALIGNED(y, 4);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     return generic_forward(*net, params, x, B, y, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -167,6 +207,10 @@ int lbdrn_forward_tape(const lbdrn_net* net, const float* params, const float* x
 {
     if (int rc = check_net(net)) return rc;
     LBDRN_REQUIRE(params && x && y && B >= 0, "null pointer or negative batch");
+    LBDRN_ALIGNED(params, 4);
+    LBDRN_ALIGNED(x, 4);
+    LBDRN_ALIGNED(y, 4);
+    LBDRN_ALIGNED(tape, ALIGN_WORKSPACE);
     NEED_DEVICE();
     return generic_forward_tape(*net, params, x, B, y, tape, tape_bytes, (hipStream_t)stream);
 }
@@ -183,6 +227,14 @@ int lbdrn_backward(const lbdrn_net* net, const float* params, const float* x, in
 {
     if (int rc = check_net(net)) return rc;
     LBDRN_REQUIRE(params && x && y && dy && grads && B >= 0, "null pointer or negative batch");
+    LBDRN_ALIGNED(params, 4);
+    LBDRN_ALIGNED(x, 4);
+    LBDRN_ALIGNED(y, 4);
+    LBDRN_ALIGNED(dy, 4);
+    LBDRN_ALIGNED(grads, 4);
+    LBDRN_ALIGNED(dx, 4);
+    LBDRN_ALIGNED(tape, ALIGN_WORKSPACE);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     return generic_backward(*net, params, x, B, tape, tape_bytes, y, dy, grads, dx, workspace, workspace_bytes,
                             (hipStream_t)stream);
@@ -213,10 +265,15 @@ int lbdrn_decode_fused(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t
                        const float* params, uint16_t* out, float* y_out, void* workspace,
                        size_t workspace_bytes, int32_t path, void* stream)
 {
-    if (int rc = check_geom(g)) return rc;
+    if (int rc = check_geom_call(g)) return rc;
     if (int rc = check_net(net)) return rc;
     if (int rc = net_matches(g, net)) return rc;
     LBDRN_REQUIRE(msb && params && out, "msb, params and out must not be null");
+    LBDRN_ALIGNED(msb, 2);
+    LBDRN_ALIGNED(params, 4);
+    LBDRN_ALIGNED(out, 2);
+    LBDRN_ALIGNED(y_out, 4);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
@@ -231,18 +288,30 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
                    const float* params, double* sse, void* workspace, size_t workspace_bytes,
                    int32_t path, void* stream)
 {
-    if (int rc = check_geom(g)) return rc;
+    if (int rc = check_geom_call(g)) return rc;
     if (int rc = check_net(net)) return rc;
     if (int rc = net_matches(g, net)) return rc;
-    LBDRN_REQUIRE(img && msb && params && sse, "img, msb, params and sse must not be null");
-    NEED_DEVICE();
+    LBDRN_REQUIRE(img && params && sse, "img, params and sse must not be null");
+    LBDRN_ALIGNED(img, 2);
+    LBDRN_ALIGNED(msb, 2);
+    LBDRN_ALIGNED(params, 4);
+    LBDRN_ALIGNED(sse, 8);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     const bool background = (path & LBDRN_EVAL_BACKGROUND) != 0, fast = (path & LBDRN_EVAL_FAST) != 0;
     const bool x16 = fast && (path & LBDRN_EVAL_X16) != 0;
     path &= ~(LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16);
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
-    if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
     const lbdrn_geom gl = launch_geom(*g);
+    // msb may be NULL exactly where the instance that will serve this call takes the colour window from img >> K: a fast
+    // instance of the fused kernels.  Host arithmetic (the plans, the C > 8 rule, serving_mode), in front of every launch: the
+    // generic path, a flagless call and a fast request that a canonical instance serves all READ msb.
+    LBDRN_REQUIRE(msb || (use_mfma && !mfma_eval_reads_msb(gl, *net, fast, x16)),
+                  "msb must not be null: %s", !fast ? "only LBDRN_EVAL_FAST leaves it unread"
+                  : !use_mfma ? "the generic path ignores LBDRN_EVAL_FAST and reads it"
+                  : "a canonical instance serves this shape's LBDRN_EVAL_FAST request and reads it");
+    NEED_DEVICE();
+    if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
     if (use_mfma)
         return mfma_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, background, fast, x16,
                              (hipStream_t)stream);
@@ -261,11 +330,14 @@ int lbdrn_train_prepare(const lbdrn_geom* g, const lbdrn_net* net, const uint16_
                         const uint16_t* msb, int32_t batch_size, void* workspace, size_t workspace_bytes,
                         int32_t path, void* stream)
 {
-    if (int rc = check_geom(g)) return rc;
+    if (int rc = check_geom_call(g)) return rc;
     if (int rc = check_net(net)) return rc;
     if (int rc = net_matches(g, net)) return rc;
     LBDRN_REQUIRE(img && msb && batch_size >= 1, "null pointer or bad batch size");
     LBDRN_REQUIRE(path >= LBDRN_PATH_AUTO && path <= LBDRN_PATH_MFMA, "unknown path %d", path);
+    LBDRN_ALIGNED(img, 2);
+    LBDRN_ALIGNED(msb, 2);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     const bool ok = mfma_train_supported(*g, *net, batch_size);
     if (path == LBDRN_PATH_MFMA && !ok) {
@@ -284,11 +356,19 @@ int lbdrn_train_epoch(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t*
                       float* losses, void* workspace, size_t workspace_bytes, int32_t path,
                       void* stream)
 {
-    if (int rc = check_geom(g)) return rc;
+    if (int rc = check_geom_call(g)) return rc;
     if (int rc = check_net(net)) return rc;
     if (int rc = net_matches(g, net)) return rc;
     LBDRN_REQUIRE(img && msb && perm && params && exp_avg && exp_avg_sq, "null pointer");
     LBDRN_REQUIRE(n >= 0 && batch_size >= 1 && adam_step0 >= 0, "bad n/batch_size/adam_step0");
+    LBDRN_ALIGNED(img, 2);
+    LBDRN_ALIGNED(msb, 2);
+    LBDRN_ALIGNED(perm, 8);
+    LBDRN_ALIGNED(params, ALIGN_TRAIN_PARAMS);
+    LBDRN_ALIGNED(exp_avg, 4);
+    LBDRN_ALIGNED(exp_avg_sq, 4);
+    LBDRN_ALIGNED(losses, 4);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     const bool alone = (path & LBDRN_TRAIN_ALONE) != 0;   // a hint (lbdrn_hip.h): performance only
     path &= ~LBDRN_TRAIN_ALONE;
@@ -332,8 +412,17 @@ int lbdrn_train_epoch_group(int32_t count, const lbdrn_geom* const* g, const lbd
     if (int rc = check_net(net)) return rc;
     for (int f = 0; f < count; ++f) {
         LBDRN_REQUIRE(g[f] && img[f] && msb[f] && perm[f] && params[f] && exp_avg[f] && exp_avg_sq[f], "null pointer (fit %d)", f);
-        if (int rc = check_geom(g[f])) return rc;
+        if (int rc = check_geom_call(g[f])) return rc;
         if (int rc = net_matches(g[f], net)) return rc;
+        // (fits are lettered A.. in these messages, so that the only number in one is the alignment)
+        LBDRN_ALIGNED_FIT(img, f, 2);
+        LBDRN_ALIGNED_FIT(msb, f, 2);
+        LBDRN_ALIGNED_FIT(perm, f, 8);
+        LBDRN_ALIGNED_FIT(params, f, ALIGN_TRAIN_PARAMS);
+        LBDRN_ALIGNED_FIT(exp_avg, f, 4);
+        LBDRN_ALIGNED_FIT(exp_avg_sq, f, 4);
+        if (losses) LBDRN_ALIGNED_FIT(losses, f, 4);
+        LBDRN_ALIGNED_FIT(workspace, f, ALIGN_WORKSPACE);
         // (K, like msb_max, may differ: only the row build of lbdrn_train_prepare reads it, and the sequential calls below
         // take g[f])
         LBDRN_REQUIRE(g[f]->C == g[0]->C && g[f]->H == g[0]->H && g[f]->W == g[0]->W &&
@@ -378,6 +467,8 @@ int lbdrn_randperm(const uint64_t* seeds, int32_t count, int64_t n, int64_t* per
                    size_t workspace_bytes, void* stream)
 {
     LBDRN_REQUIRE(n >= 0 && (perm || n == 0), "bad n or null output");
+    LBDRN_ALIGNED(perm, 8);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     return randperm_batch(seeds, count, n, perm, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -395,6 +486,10 @@ int lbdrn_plane_encode(const uint16_t* planes, int32_t C, int32_t H, int32_t W, 
                        uint64_t* body_bytes, void* workspace, size_t workspace_bytes, void* stream)
 {
     LBDRN_REQUIRE(C >= 1 && H >= 1 && W >= 1 && C <= 65535, "bad raster geometry");
+    LBDRN_ALIGNED(planes, 2);
+    if (int rc = plane_body_aligned(body)) return rc;
+    LBDRN_ALIGNED(body_bytes, 8);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     return plane_encode(planes, C, H, W, body, body_capacity, body_bytes, workspace, workspace_bytes,
                         (hipStream_t)stream);
@@ -404,6 +499,10 @@ int lbdrn_plane_decode(const void* body, size_t body_bytes, int32_t C, int32_t H
                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream)
 {
     LBDRN_REQUIRE(C >= 1 && H >= 1 && W >= 1 && C <= 65535, "bad raster geometry");
+    if (int rc = plane_body_aligned(body)) return rc;
+    LBDRN_ALIGNED(planes, 2);
+    LBDRN_ALIGNED(status, 4);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     return plane_decode(body, body_bytes, C, H, W, planes, status, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -415,6 +514,8 @@ size_t lbdrn_jp2k_workspace(int32_t C, int32_t H, int32_t W) { return jp2k_works
 int lbdrn_jp2k_encode(const uint16_t* planes, int32_t C, int32_t H, int32_t W, int32_t bits, void* out, size_t capacity,
                       size_t* nbytes, void* workspace, size_t workspace_bytes, void* stream)
 {
+    LBDRN_ALIGNED(planes, 2);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     if (int rc = device_ok()) return rc;
     return jp2k_encode(planes, C, H, W, bits, (uint8_t*)out, capacity, nbytes, workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -425,6 +526,7 @@ int lbdrn_weights_encode(const float* values, int64_t n, int32_t precision, void
 {
     LBDRN_REQUIRE((values || n == 0) && out && nbytes && n >= 0 && n < ((int64_t)1 << 32), "null pointer or bad count");
     LBDRN_REQUIRE(precision == 0 || (precision >= 2 && precision <= 32), "precision %d is not 0 or 2..32", precision);
+    LBDRN_ALIGNED(values, 4);
     return weights_encode(values, n, precision, (uint8_t*)out, capacity, nbytes);
 }
 
@@ -440,6 +542,7 @@ int lbdrn_weights_info(const void* stream, size_t nbytes, int64_t* n, int32_t* p
 int lbdrn_weights_decode(const void* stream, size_t nbytes, float* values, int64_t capacity)
 {
     LBDRN_REQUIRE(stream && (values || capacity == 0) && capacity >= 0, "null pointer or bad capacity");
+    LBDRN_ALIGNED(values, 4);
     return weights_decode((const uint8_t*)stream, nbytes, values, capacity);
 }
 
@@ -451,6 +554,14 @@ int lbdrn_train_step(const lbdrn_net* net, const float* x, const float* t, int32
     if (int rc = check_net(net)) return rc;
     LBDRN_REQUIRE(x && t && params, "x, t and params must not be null");
     LBDRN_REQUIRE(!apply_adam || (exp_avg && exp_avg_sq && adam_step >= 1), "Adam state missing or adam_step < 1");
+    LBDRN_ALIGNED(x, 4);
+    LBDRN_ALIGNED(t, 4);
+    LBDRN_ALIGNED(params, 4);
+    LBDRN_ALIGNED(exp_avg, 4);
+    LBDRN_ALIGNED(exp_avg_sq, 4);
+    LBDRN_ALIGNED(loss, 4);
+    LBDRN_ALIGNED(grads, 4);
+    LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     NEED_DEVICE();
     return generic_train_step(*net, x, t, B, params, exp_avg, exp_avg_sq, adam_step, lr, apply_adam,
                               loss, grads, workspace, workspace_bytes, (hipStream_t)stream);

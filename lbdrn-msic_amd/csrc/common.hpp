@@ -122,6 +122,8 @@ int mfma_decode(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* msb, 
 int mfma_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                   const uint16_t* msb, const float* params, double* sse, void* ws, size_t ws_bytes,
                   bool background, bool fast, bool x16, hipStream_t s);
+// whether the instance that serves this evaluation request reads msb (host arithmetic; false: it takes img >> K)
+bool mfma_eval_reads_msb(const lbdrn_geom& g, const lbdrn_net& net, bool fast, bool x16);
 
 int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net, const int64_t* const* perm, int64_t n,
                            int bs, float* const* params, float* const* m, float* const* v, int64_t step0, double lr,

@@ -649,7 +649,7 @@ static size_t carve_train(const lbdrn_net& net, int B, void* ws, TrainWs* w)
     char* dz0 = take((size_t)B * net.bc * sizeof(float));
     char* dz1 = take((size_t)B * net.bc * sizeof(float));
     char* gr = take((size_t)param_count(net) * sizeof(float));
-    const size_t nsl = (size_t)(B + GRAD_SLICE - 1) / GRAD_SLICE;
+    const size_t nsl = ((size_t)B + GRAD_SLICE - 1) / GRAD_SLICE;   // (in size_t: B + GRAD_SLICE - 1 leaves int near INT_MAX)
     const size_t rows = (size_t)std::max(net.bc, net.C), cols = (size_t)std::max(net.bc, net.F) + 1;
     char* sl = take(nsl * rows * cols * sizeof(float));
     char* pa = take(LOSS_BLOCKS * sizeof(double));

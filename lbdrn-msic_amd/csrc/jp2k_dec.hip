@@ -213,6 +213,8 @@ static int jp2kd_device_ok()
 static int jp2kd_decode(const void* buf, size_t n, uint16_t* planes, int C, int H, int W, void* ws, size_t ws_bytes, hipStream_t s)
 {
     LBDRN_REQUIRE(buf && planes, "lbdrn_jp2kd_decode: null pointer");
+    LBDRN_REQUIRE(((uintptr_t)planes & 1u) == 0, "lbdrn_jp2kd_decode: planes is not 2-byte aligned");
+    LBDRN_REQUIRE(((uintptr_t)ws & 255u) == 0, "lbdrn_jp2kd_decode: workspace is not 256-byte aligned");   // (carve_jp2kd: int32 regions from the base)
     jp2k::DecStream st;
     int64_t nblocks = 0;
     if (int rc = jp2kd_open(buf, n, &st, &nblocks, "lbdrn_jp2kd_decode")) return rc;

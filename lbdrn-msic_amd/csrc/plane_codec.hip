@@ -264,10 +264,19 @@ size_t plane_workspace(int C, int H, int W)
     return w.total;
 }
 
+// The body is counts[] then the words, both read and written as uint32_t (the casts below, k_plane_compact, k_plane_decode):
+// a body at an odd or 2-byte aligned address is refused, like lbdrn_plane3.h's.  No device needed: the entry points ask first.
+int plane_body_aligned(const void* body)
+{
+    LBDRN_REQUIRE(((uintptr_t)body & 3) == 0, "body must be 4-byte aligned (lbdrn_hip.h: Alignment)");
+    return 0;
+}
+
 int plane_encode(const uint16_t* planes, int C, int H, int W, void* body, size_t body_cap, uint64_t* body_bytes,
                  void* ws, size_t ws_bytes, hipStream_t s)
 {
     LBDRN_REQUIRE(planes && body && body_bytes && C >= 1 && H >= 1 && W >= 1, "null pointer or empty raster");
+    if (int rc = plane_body_aligned(body)) return rc;
     const PlaneGeom g = plane_geom(C, H, W);
     PlaneWs w;
     if (int rc = carve_plane(g, ws, &w)) return rc;
@@ -294,6 +303,7 @@ int plane_decode(const void* body, size_t body_bytes, int C, int H, int W, uint1
                  size_t ws_bytes, hipStream_t s)
 {
     LBDRN_REQUIRE(planes && body && status && C >= 1 && H >= 1 && W >= 1, "null pointer or empty raster");
+    if (int rc = plane_body_aligned(body)) return rc;
     const PlaneGeom g = plane_geom(C, H, W);
     PlaneWs w;
     if (int rc = carve_plane(g, ws, &w)) return rc;

@@ -248,6 +248,10 @@ static int resid_encode(const uint16_t* orig, const uint16_t* recon, int C, int 
                         uint64_t* body_bytes, void* ws, size_t ws_bytes, hipStream_t s)
 {
     LBDRN_REQUIRE(orig && recon && body && body_bytes, "lbdrn_resid_encode: null pointer");
+    LBDRN_REQUIRE(((uintptr_t)orig & 1u) == 0, "lbdrn_resid_encode: orig is not 2-byte aligned");
+    LBDRN_REQUIRE(((uintptr_t)recon & 1u) == 0, "lbdrn_resid_encode: recon is not 2-byte aligned");
+    LBDRN_REQUIRE(((uintptr_t)body_bytes & 7u) == 0, "lbdrn_resid_encode: body_bytes is not 8-byte aligned");
+    LBDRN_REQUIRE(((uintptr_t)ws & 255u) == 0, "lbdrn_resid_encode: workspace is not 256-byte aligned");   // (carve_resid: u32 / u64 regions at multiples of 256)
     LBDRN_REQUIRE(tau >= 0 && tau <= 65535, "lbdrn_resid_encode: tau = %d is outside 0..65535", tau);
     resid::Geom g;
     LBDRN_REQUIRE(resid::make_geom(C, H, W, &g), "lbdrn_resid_encode: geometry %d x %d x %d is out of range", C, H, W);
@@ -276,6 +280,9 @@ static int resid_decode(const void* body, size_t n, int C, int H, int W, int x0,
                         int* status, void* ws, size_t ws_bytes, hipStream_t s)
 {
     LBDRN_REQUIRE(body && recon && status, "lbdrn_resid_decode: null pointer");
+    LBDRN_REQUIRE(((uintptr_t)recon & 1u) == 0, "lbdrn_resid_decode: recon_inout is not 2-byte aligned");
+    LBDRN_REQUIRE(((uintptr_t)status & 3u) == 0, "lbdrn_resid_decode: status is not 4-byte aligned");
+    LBDRN_REQUIRE(((uintptr_t)ws & 255u) == 0, "lbdrn_resid_decode: workspace is not 256-byte aligned");
     resid::Geom g;
     LBDRN_REQUIRE(resid::make_geom(C, H, W, &g), "lbdrn_resid_decode: geometry %d x %d x %d is out of range", C, H, W);
     LBDRN_REQUIRE(rw >= 1 && rh >= 1 && x0 >= 0 && y0 >= 0 && x0 <= W - rw && y0 <= H - rh,

@@ -131,6 +131,8 @@ static int tiff_decode(const lbdrn_tiff_layout* L, const void* file, size_t file
                        size_t nseg, void* planes, int32_t* status, void* ws, size_t ws_bytes, hipStream_t s)
 {
     LBDRN_REQUIRE(L && file && offsets && counts && planes && status, "lbdrn_tiff_decode: null pointer");
+    LBDRN_REQUIRE(((uintptr_t)status & 3u) == 0, "lbdrn_tiff_decode: status is not 4-byte aligned");
+    LBDRN_REQUIRE(((uintptr_t)ws & 255u) == 0, "lbdrn_tiff_decode: workspace is not 256-byte aligned");   // (carve_tiff: u64 regions at multiples of 256)
     tiff::Geom g;
     LBDRN_REQUIRE(tiff::make_geom(*L, &g), "lbdrn_tiff_decode: the layout is out of range");
     LBDRN_REQUIRE((int64_t)nseg == g.nseg, "lbdrn_tiff_decode: %zu segments given, the layout has %lld", nseg, (long long)g.nseg);
@@ -143,6 +145,7 @@ static int tiff_decode(const lbdrn_tiff_layout* L, const void* file, size_t file
                   tiff::segment_cap(g.compression), g.compression);
         return LBDRN_E_UNSUPPORTED;
     }
+    LBDRN_REQUIRE(g.bps == 1 || ((uintptr_t)planes & 1u) == 0, "lbdrn_tiff_decode: planes is not 2-byte aligned");   // (16-bit samples)
     TiffWs w;
     carve_tiff(g, ws, &w);
     if (!ws || ws_bytes < w.total) {

@@ -265,6 +265,13 @@ struct TrainWsLayout {
     size_t off_rows, off_pack, off_slab, slab_bytes, off_loss, off_stage, stage_bytes, off_map, total;
 };
 
+// workgroups (= slabs, loss partials) of one step of bs rows, for whichever kernel steps.  In size_t: bs + TB - 1 leaves int at
+// the minibatch sizes lbdrn_train_workspace is asked about (any -bs up to INT_MAX)
+static size_t step_workgroups(int bs)
+{
+    return std::max(((size_t)bs + TB - 1) / TB, 2 * (((size_t)bs + WB - 1) / WB));
+}
+
 static TrainWsLayout train_ws_layout(const lbdrn_geom& g, const lbdrn_net& net, const TrainPlan& p, int bs)
 {
     TrainWsLayout L;
@@ -273,7 +280,7 @@ static TrainWsLayout train_ws_layout(const lbdrn_geom& g, const lbdrn_net& net, 
     L.off_pack = o; o += align_up((size_t)p.pack_floats * sizeof(float), 256);
     // slabs / loss partials: one per workgroup of whichever kernel steps -- 32-row workgroups (the tile kernel), 64-row ones
     // (k_train_stream), or two per 64-row group (k_train_split)
-    const size_t nwg = std::max((size_t)(bs + TB - 1) / TB, 2 * ((size_t)(bs + WB - 1) / WB));
+    const size_t nwg = step_workgroups(bs);
     L.slab_bytes = align_up(nwg * (size_t)p.slab_floats * sizeof(float), 256);
     L.off_slab = o; o += SLAB_ROT * L.slab_bytes;
     L.off_loss = o; o += align_up(nwg * sizeof(double), 256);
@@ -290,7 +297,7 @@ static TrainWsLayout train_ws_layout(const lbdrn_geom& g, const lbdrn_net& net, 
 // generic step (LBDRN_PATH_AUTO) or are refused (LBDRN_PATH_MFMA): ADVICE round 5.
 static bool slabs_addressable(const TrainPlan& p, int bs)
 {
-    const size_t nwg = std::max((size_t)(bs + TB - 1) / TB, 2 * ((size_t)(bs + WB - 1) / WB));
+    const size_t nwg = step_workgroups(bs);
     return nwg * (size_t)p.slab_floats * sizeof(float) < ((size_t)1 << 31);
 }
 

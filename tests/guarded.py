@@ -12,7 +12,12 @@ The fills:
     0xA5  a denormal-sized negative float (-2.87e-16), a large integer
 A region whose initialisation is missing differs under at least one of them.
 
+A buffer may also be placed OFF its alignment on purpose (tests/test_gpu_call_shapes.py): `skew` bytes past a multiple of
+`align`, so that a caller's pointer is aligned to what include/lbdrn_hip.h asks of that argument and to nothing more.  A
+test that reuses code which builds its own Arena states the skews once, by buffer name, with `placement(fn)`.
+
 Works on any device (tests/test_guarded_host.py runs it on CPU tensors).  A plain module: no fixture, no marker."""
+import contextlib
 import ctypes
 
 import torch
@@ -36,14 +41,15 @@ class GuardError(AssertionError):
 
 
 class Buf:
-    """`nbytes` of device memory at a 256-byte aligned address, between two guards in the same tensor."""
+    """`nbytes` of device memory at an address `skew` bytes past a multiple of `align` (256-byte aligned as the Arena hands
+    them out by default), between two guards in the same tensor."""
 
-    def __init__(self, name, nbytes, fill, align, dev):
-        assert nbytes >= 0 and align >= 1 and 0 <= fill <= 0xFF
-        self.name, self.nbytes, self.fill, self.align = name, int(nbytes), fill, align
+    def __init__(self, name, nbytes, fill, align, dev, skew=0):
+        assert nbytes >= 0 and align >= 1 and 0 <= fill <= 0xFF and 0 <= skew < align
+        self.name, self.nbytes, self.fill, self.align, self.skew = name, int(nbytes), fill, align, int(skew)
         self.whole = torch.empty(GUARD + align + self.nbytes + GUARD, dtype=torch.uint8, device=dev)
         base = self.whole.data_ptr()
-        self.start = GUARD + (-(base + GUARD)) % align          # first aligned offset with a whole guard in front of it
+        self.start = GUARD + (skew - (base + GUARD)) % align    # first offset at that residue with a whole guard in front of it
         self.end = self.start + self.nbytes
         self.whole.fill_(guard_byte(fill))
         self.t = self.whole[self.start:self.end]                # the interior, a view
@@ -113,6 +119,21 @@ class Buf:
         return None
 
 
+_PLACEMENT = None     # name -> skew, for the buffers of every Arena built inside `with placement(fn)`
+
+
+@contextlib.contextmanager
+def placement(fn):
+    """Inside the block every Arena places a buffer whose `skew` is not given at fn(name) bytes past a multiple of its
+    alignment: one statement of where each argument of a call lies, for code that builds its Arena itself."""
+    global _PLACEMENT
+    before, _PLACEMENT = _PLACEMENT, fn
+    try:
+        yield
+    finally:
+        _PLACEMENT = before
+
+
 class Arena:
     """Every buffer a test hands to the library: guarded, filled, and checked together."""
 
@@ -120,17 +141,21 @@ class Arena:
         self.dev = torch.device(dev)
         self.bufs = []
         self.consts = []
+        self.placement = _PLACEMENT
 
-    def buf(self, nbytes, fill, align=256, name=None):
-        b = Buf(name or f"buf{len(self.bufs)}", nbytes, fill, align, self.dev)
+    def buf(self, nbytes, fill, align=256, name=None, skew=None):
+        name = name or f"buf{len(self.bufs)}"
+        if skew is None:
+            skew = self.placement(name) if self.placement else 0
+        b = Buf(name, nbytes, fill, align, self.dev, skew)
         self.bufs.append(b)
         return b
 
-    def const(self, array, name=None):
+    def const(self, array, name=None, skew=None):
         """an input the call must not change: a guarded buffer holding `array`, remembered for check_consts()"""
         import numpy as np
         a = np.ascontiguousarray(array)
-        b = self.buf(a.nbytes, 0x00, name=name or f"const{len(self.consts)}").write(a)
+        b = self.buf(a.nbytes, 0x00, name=name or f"const{len(self.consts)}", skew=skew).write(a)
         self.consts.append((b, a.reshape(-1).view(np.uint8).copy()))
         return b
 

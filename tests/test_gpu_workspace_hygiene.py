@@ -16,9 +16,9 @@ of its scratch AND its output buffers, on the same inputs, through ctypes so tha
 
 The test ids read <entry point>-<kernel family / shape>-<fill>.  Within a case the 0x00 fill runs first.
 
-lbdrn_eval_sse and *sse: the header does not say whether the call overwrites *sse or adds to it.  csrc/generic.hip
-(k_sum_partials with accumulate = 0 on the first chunk) and csrc/apply_mfma.hip (k_sum_partials_mfma: `*dst = s`)
-OVERWRITE it on every path, so *sse is an output like any other here: it is poisoned with the fill before the call."""
+lbdrn_eval_sse and *sse: the header says the call OVERWRITES *sse on every path (csrc/generic.hip: k_sum_partials with
+accumulate = 0 on the first chunk; csrc/apply_mfma.hip: k_sum_partials_mfma, `*dst = s`), so *sse is an output like any
+other here: it is poisoned with the fill before the call."""
 import ctypes
 import struct
 

@@ -39,6 +39,52 @@ def test_carving_is_aligned_disjoint_and_filled_only_inside(nbytes, fill):
     a.check()
 
 
+@pytest.mark.parametrize("fill", FILLS, ids=guarded.fill_id)
+@pytest.mark.parametrize("skew", [0, 2, 4, 8, 16, 254, 255])
+def test_a_skewed_interior_starts_that_far_past_the_alignment_with_whole_guards(skew, fill):
+    """skew bytes past a multiple of `align` and not a byte better than the skew says; fills, guards and the damage report
+    are those of an aligned buffer"""
+    a = Arena("cpu")
+    x = np.arange(101, dtype=np.uint16)
+    bufs = [a.buf(1001, fill, name="skewed", skew=skew), a.buf(64, fill, align=512, name="wide", skew=skew),
+            a.const(x, name="x", skew=skew)]
+    for b in bufs:
+        assert b.skew == skew and b.data_ptr() % b.align == skew
+        if skew:       # aligned to the skew's own lowest set bit, to nothing above it
+            assert b.data_ptr() % (2 * (skew & -skew)) != 0
+        assert b.start >= GUARD and b.whole.numel() - b.end >= GUARD
+        assert b.t.numel() == b.nbytes and b.t.data_ptr() == b.data_ptr() == b.ptr.value
+        whole = b.whole.numpy()
+        assert (whole[:b.start] == guard_byte(b.fill)).all() and (whole[b.end:] == guard_byte(b.fill)).all()
+    assert (bufs[0].whole.numpy()[bufs[0].start:bufs[0].end] == fill).all()
+    assert np.array_equal(bufs[2].numpy(np.uint16), x)
+    a.check()
+    bufs[0].whole[bufs[0].start - 1] = 0x11
+    assert bufs[0].guard_damage() == ("front", -1)
+    bufs[2].whole[bufs[2].start + 3] ^= 1
+    with pytest.raises(GuardError) as e:
+        a.check_consts()
+    assert "'x'" in str(e.value) and "byte 3" in str(e.value)
+    with pytest.raises(AssertionError):
+        a.buf(8, fill, align=16, skew=16)                                     # a skew is less than the alignment
+
+
+def test_placement_states_the_skews_by_name_for_arenas_built_inside_it():
+    table = {"planes": 2, "params": 16}
+    with guarded.placement(lambda name: table.get(name, 0)):
+        a = Arena("cpu")
+        assert a.buf(10, 0x00, name="planes").data_ptr() % 256 == 2
+        assert a.const(np.zeros(3, np.float32), name="params").data_ptr() % 256 == 16
+        assert a.buf(10, 0x00, name="workspace").data_ptr() % 256 == 0
+        assert a.buf(10, 0x00, name="planes", skew=0).data_ptr() % 256 == 0      # an explicit skew wins
+        with guarded.placement(None):
+            assert Arena("cpu").buf(10, 0x00, name="planes").data_ptr() % 256 == 0
+        assert Arena("cpu").buf(10, 0x00, name="planes").data_ptr() % 256 == 2
+    assert Arena("cpu").buf(10, 0x00, name="planes").data_ptr() % 256 == 0        # and nothing stays behind
+    assert a.buf(10, 0x00, name="planes").data_ptr() % 256 == 2                   # an Arena keeps the placement it was built under
+    a.check()
+
+
 def test_typed_views_share_the_interior():
     a = Arena("cpu")
     b = a.buf(64, 0x00, name="typed")
