@@ -4,6 +4,13 @@ the files libtiff wrote, the workspace's hygiene on guarded buffers, a fixed lis
 entry points: raster_io, encode.py and decode.py give from a tiled Deflate predictor-2 BigTIFF what they give from its
 uncompressed twin.  Every comparison is exact equality with the source array.
 
+Segment sizes and stream sources here: the largest compressed segment of the base raster is about 31 KB, below Deflate's
+32 KiB history ring; the hard cases add a constant raster of 78 KB strips (distance-1 matches only), 7.8 KB of noise and
+one 25.6 KB LZW strip; every stream comes from tests/tiff_reference.py (zlib level 9 / Z_FIXED / level 0, the textbook LZW
+and PackBits coders) or from libtiff (the golden files).  Segments of a scene's size -- 128 KiB to the caps of 768 KiB, 384 KiB
+and 1 MiB of PackBits, zlib levels 1 / 6 / 9, hand-assembled blocks at the ring's edge, codes of 11 to 15 bits, damage beyond
+the ring -- are tests/test_gpu_tiff_big.py, on the case table of tests/tiff_big_cases.py.
+
 Every file here except the uncompressed-strip control raised ValueError in raster_io before the library existed."""
 import ctypes
 import os

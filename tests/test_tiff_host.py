@@ -4,7 +4,9 @@ layout; the reference decoders against files libtiff wrote (tests/golden/tiff_li
 segment against the reference; the ValueErrors for everything outside the subset; the library's checks that come before any
 launch; the kernels' resource usage; the host path of an oversize Deflate strip; raster_io.read_raster end to end with the device stage replaced by the
 host shim; and tests/tiff_damage_main.cpp, a stand-alone program built with AddressSanitizer and
-UndefinedBehaviorSanitizer, which feeds the host decoders damaged streams.  No GPU.  Every comparison is exact."""
+UndefinedBehaviorSanitizer, which feeds the host decoders damaged streams -- and, once each, the scene-sized segments of
+tests/tiff_big_cases.py, sound and damaged (tests/test_tiff_host_big.py runs that table through the shim).  No GPU.  Every
+comparison is exact."""
 import ctypes
 import os
 import shutil
@@ -443,8 +445,17 @@ def test_damaged_segments_under_sanitizers_in_a_program_of_its_own(tmp_path):
         for _, bad in R.damage_cases(comp, R.compress(raw, comp, row_bytes=106), len(raw)):
             rec(2, comp, len(raw), bad)
             nfixed += 1
+    # segments of a scene's size (tests/tiff_big_cases.py): every sound row once, and the damaged large segments
+    import tiff_big_cases as B
+    for _, comp, stream, want in B.rows():
+        rec(3, comp, len(want), stream, want)
+    for _, comp, bad, _, _, want in B.damage_rows():
+        rec(2, comp, len(want), bad)
+        nfixed += 1
     cases = tmp_path / "cases.bin"
     cases.write_bytes(b"".join(recs))
     run = subprocess.run([exe, str(cases)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
-    assert f"{nfixed} of the fixed list flagged" in run.stdout and "ERROR" not in run.stderr
+    nsound = sum(r[0] in (1, 3) for r in recs)
+    assert nsound == 11 + len(B.rows())
+    assert f"{nsound} sound streams, {nfixed} of the fixed list flagged" in run.stdout and "ERROR" not in run.stderr

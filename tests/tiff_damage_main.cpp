@@ -9,7 +9,10 @@
 //     kind | compression | expected bytes | stream bytes | the stream | the expected bytes (kind 1 only)
 // kind 1: a sound stream.  It must decode to the expected bytes; then `cuts` truncations and `flips` single-byte
 //         corruptions of it are decoded (400 and 1,000 per codec, shared among the codec's streams).
-// kind 2: a damaged stream of the fixed list (tiff_reference.damage_cases).  It must end in a non-zero status.
+// kind 2: a damaged stream of the fixed lists (tiff_reference.damage_cases, tiff_big_cases.damage_rows).  It must end in a
+//         non-zero status.
+// kind 3: a sound stream of a scene-sized segment (tiff_big_cases.rows; the expected bytes follow as for kind 1).  It must
+//         decode to the expected bytes and is decoded once: the random damage is drawn on the small streams of kind 1.
 // Exit 0 and a line of counts when every damaged stream ended in a status or in a completed decode, non-zero otherwise.
 #include <stdio.h>
 
@@ -53,7 +56,7 @@ int main(int argc, char** argv)
         if (!get32(f, &c.comp) || !get32(f, &c.expect) || !get32(f, &n)) return 2;
         c.stream.resize(n);
         if (n && fread(c.stream.data(), 1, n, f) != n) return 2;
-        if (kind == 1) {
+        if (kind == 1 || kind == 3) {
             c.want.resize(c.expect);
             if (fread(c.want.data(), 1, c.expect, f) != c.expect) return 2;
         }
@@ -77,6 +80,7 @@ int main(int argc, char** argv)
             std::vector<uint8_t> got;
             if (run((int)c.comp, c.stream, c.expect, &got) != 0 || got != c.want) { fprintf(stderr, "a sound stream did not decode\n"); return 5; }
             ++sound;
+            if (c.kind == 3) continue;
             const uint32_t n = (uint32_t)c.stream.size();
             for (int t = 0; t < cuts; ++t) {
                 std::vector<uint8_t> cut(c.stream.begin(), c.stream.begin() + (size_t)(rnd() % n));

@@ -34,11 +34,14 @@ class _MsbWriter:
         return bytes(self.out)
 
 
-def lzw_encode(data):
+def lzw_code_list(data, clear=True):
+    """[(code, width)] of the stream lzw_encode writes, the leading Clear and the EOI included.  clear=False: the coder never
+    sends a second Clear; once the table holds its 4096 codes it adds no entry and goes on with 12-bit codes (TIFF 6.0 lets
+    a writer do that; a reader's table then stays as it is)."""
     data = bytes(data)
-    w = _MsbWriter()
+    out = []
     table, nxt, width = {}, 258, 9
-    w.put(CLEAR, width)
+    out.append((CLEAR, width))
     cur = None      # code of the string matched so far
     for c in data:
         if cur is None:
@@ -48,25 +51,39 @@ def lzw_encode(data):
         if key in table:
             cur = table[key]
             continue
-        w.put(cur, width)
-        table[key] = nxt
-        nxt += 1
-        if nxt == 4094:
-            w.put(CLEAR, width)
-            table, nxt, width = {}, 258, 9
-        elif nxt in (512, 1024, 2048):
-            width += 1
+        out.append((cur, width))
+        if nxt < 4096:
+            table[key] = nxt
+            nxt += 1
+            if nxt == 4094 and clear:
+                out.append((CLEAR, width))
+                table, nxt, width = {}, 258, 9
+            elif nxt in (512, 1024, 2048):
+                width += 1
         cur = c
     if cur is not None:
-        w.put(cur, width)
-        nxt += 1
-        if nxt == 4094:
-            w.put(CLEAR, width)
-            width = 9
-        elif nxt in (512, 1024, 2048):
-            width += 1
-    w.put(EOI, width)
+        out.append((cur, width))
+        if nxt < 4096:
+            nxt += 1
+            if nxt == 4094 and clear:
+                out.append((CLEAR, width))
+                width = 9
+            elif nxt in (512, 1024, 2048):
+                width += 1
+    out.append((EOI, width))
+    return out
+
+
+def lzw_pack(codes):
+    """[(code, width)] -> the stream's bytes, MSB first"""
+    w = _MsbWriter()
+    for code, width in codes:
+        w.put(code, width)
     return w.finish()
+
+
+def lzw_encode(data, clear=True):
+    return lzw_pack(lzw_code_list(data, clear))
 
 
 def lzw_decode(data, expect):
