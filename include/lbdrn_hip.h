@@ -206,6 +206,21 @@ int lbdrn_eval_sse(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t *im
                    const uint16_t *msb, const float *params, double *sse, void *workspace,
                    size_t workspace_bytes, int32_t path, void *stream);
 
+/* DIAGNOSTIC (tests/test_apply_plan_host.py, tests/test_gpu_apply_instances.py): which instance of the fused apply pass serves a
+ * request, and on what plan -- host arithmetic only, no device needed, nothing launched; g and net pass the checks of the two entry points
+ * (with P > 0 the tables are present; neither is read).  path_word is the `path` word of lbdrn_eval_sse (LBDRN_EVAL_FAST and LBDRN_EVAL_X16 are read,
+ * LBDRN_EVAL_BACKGROUND changes the grid and no instance), or path | LBDRN_APPLY_DECODE for the request lbdrn_decode_fused
+ * makes.  The answer is what LBDRN_PATH_MFMA runs (and LBDRN_PATH_AUTO with it); where LBDRN_PATH_MFMA answers
+ * LBDRN_E_UNSUPPORTED so does this, and out is left as it was.  out[0] family: 1 k_apply_mfma (weights resident in LDS), 2
+ * k_apply_wide (weights streamed); out[1] NT: hidden tiles, bc / 32 (family 1) or bc / 16 (family 2); out[2] family 1: 1 for
+ * the ReLU instance, 0 for Sine; family 2: NL, the hidden layers; out[3] the mode of the serving instance: 0 decode, 1
+ * canonical evaluation, 2 fast, 3 exact-operand -- msb may be NULL in lbdrn_eval_sse exactly where this is 2 or 3; out[4] TH,
+ * the rows of a tile (tiles are 64 columns wide); out[5] family 1: `pair`, layer 0 walks the colour features in channel pairs;
+ * family 2: `skip`, layer 0 leaves the window centres out; out[6] `x16`: the plan has the exact-operand layer 0; out[7] the
+ * tiles of the raster, ceil(W / 64) * ceil(H / TH).  Additive: the ABI version did not change with it. */
+#define LBDRN_APPLY_DECODE 0x2000
+int lbdrn_apply_instance(const lbdrn_geom *g, const lbdrn_net *net, int32_t path_word, int32_t *out);
+
 /* a4+a5+a7+a8 -- one trainer epoch (encode.py:69-70,157; modified_ignite_engine.py:18-27;
  * torch.optim.Adam defaults, encode.py:84): for each minibatch perm[s*bs .. min((s+1)*bs,n))
  * of pixel indices: gather features and labels, forward, MSE loss, backward, Adam update of

@@ -972,8 +972,8 @@ static int run_wapply(const ApplyCall& c, int mode)
 // says, and mfma_eval_reads_msb answers lbdrn_eval_sse's NULL-msb check from it before anything is launched.
 static int resolve_apply(const lbdrn_geom& g, const lbdrn_net& net, int mode, ApplyPlan* plan, int* wide_mode)
 {
-    if (mode == MODE_EVAL_X16) {   // (a hint: where the x16 weight pack does not fit in LDS, or fits only at a shorter tile than the fast
-                                   //  plan's -- C = 8, D = 3, bc = 64 --, the pass is the fast one)
+    if (mode == MODE_EVAL_X16) {   // (a hint: where the x16 weight pack does not fit in LDS -- C = 8, D = 3, bc = 64 --, or fits only at a
+                                   //  shorter tile than the fast plan's -- C = 6, D = 3, bc = 64, two layers --, the pass is the fast one)
         ApplyPlan fp, xp;
         if (make_plan(g, net, &fp, true, false) && (!make_plan(g, net, &xp, true, true) || xp.TH < fp.TH)) mode = MODE_EVAL_FAST;
     }
@@ -1003,6 +1003,26 @@ bool mfma_eval_reads_msb(const lbdrn_geom& g, const lbdrn_net& net, bool fast, b
         if (!resolve_wapply(g, net, wide_mode, &wp, &mode)) return true;   // (no fused instance: the call is refused later)
     }
     return !mode_fast(mode);
+}
+
+// lbdrn_apply_instance (lbdrn_hip.h): what run_apply would launch for the request, read off the same two functions and launched
+// nowhere.  request: 0 decode, 1 evaluation, 2 with LBDRN_EVAL_FAST, 3 with LBDRN_EVAL_X16 too (ApplyMode).  false: no fused instance.
+bool mfma_apply_instance(const lbdrn_geom& g, const lbdrn_net& net, int request, int32_t out[8])
+{
+    ApplyPlan p;
+    int wide_mode = -1;
+    const int serving = resolve_apply(g, net, request, &p, &wide_mode);
+    if (wide_mode < 0) {
+        const int32_t v[8] = {1, p.NT, net.act == LBDRN_ACT_RELU, serving, p.TH, p.pair, p.x16, p.tiles_x * p.tiles_y};
+        std::copy(v, v + 8, out);
+        return true;
+    }
+    WApplyPlan w;
+    int wserving = wide_mode;
+    if (!resolve_wapply(g, net, wide_mode, &w, &wserving)) return false;
+    const int32_t v[8] = {2, w.NT, net.nl, wserving, w.TH, w.skip, 0, w.tiles_x * w.tiles_y};
+    std::copy(v, v + 8, out);
+    return true;
 }
 
 static int run_apply(const ApplyCall& c, int mode)

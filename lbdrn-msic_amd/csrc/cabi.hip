@@ -318,6 +318,25 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
     return generic_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int lbdrn_apply_instance(const lbdrn_geom* g, const lbdrn_net* net, int32_t path_word, int32_t* out)
+{
+    if (int rc = check_geom(g)) return rc;
+    if (int rc = check_net(net)) return rc;
+    if (int rc = net_matches(g, net)) return rc;
+    LBDRN_REQUIRE(out, "out must not be null");
+    const bool decode = (path_word & LBDRN_APPLY_DECODE) != 0, fast = (path_word & LBDRN_EVAL_FAST) != 0;
+    const bool x16 = fast && (path_word & LBDRN_EVAL_X16) != 0;
+    LBDRN_REQUIRE(!(decode && fast), "LBDRN_APPLY_DECODE takes no evaluation flag");
+    const int32_t path = path_word & ~(LBDRN_APPLY_DECODE | LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16);
+    LBDRN_REQUIRE(path >= LBDRN_PATH_AUTO && path <= LBDRN_PATH_MFMA, "unknown path %d", path);
+    // (the request as ApplyMode counts it: the decode pass, the canonical evaluation, the fast one, the exact-operand one)
+    if (!mfma_apply_supported(*g, *net) || !mfma_apply_instance(launch_geom(*g), *net, decode ? 0 : fast ? (x16 ? 3 : 2) : 1, out)) {
+        set_error("fused MFMA apply kernel does not support bc=%d nl=%d C=%d D=%d", net->bc, net->nl, net->C, g->D);
+        return LBDRN_E_UNSUPPORTED;
+    }
+    return 0;
+}
+
 size_t lbdrn_train_workspace(const lbdrn_geom* g, const lbdrn_net* net, int32_t batch_size)
 {
     if (check_geom(g) || check_net(net) || batch_size < 1) return 0;

@@ -124,6 +124,8 @@ int mfma_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img
                   bool background, bool fast, bool x16, hipStream_t s);
 // whether the instance that serves this evaluation request reads msb (host arithmetic; false: it takes img >> K)
 bool mfma_eval_reads_msb(const lbdrn_geom& g, const lbdrn_net& net, bool fast, bool x16);
+// which instance serves a request (0 decode, 1 evaluation, 2 fast, 3 exact-operand) and on what plan: lbdrn_apply_instance's out[8]
+bool mfma_apply_instance(const lbdrn_geom& g, const lbdrn_net& net, int request, int32_t out[8]);
 
 int mfma_train_epoch_group(int count, const lbdrn_geom& g, const lbdrn_net& net, const int64_t* const* perm, int64_t n,
                            int bs, float* const* params, float* const* m, float* const* v, int64_t step0, double lr,

@@ -806,7 +806,7 @@ def test_every_device_entry_point_of_the_header_has_a_case():
                       "lbdrn_decode_fused", "lbdrn_eval_sse", "lbdrn_train_prepare", "lbdrn_train_epoch", "lbdrn_train_epoch_group",
                       "lbdrn_randperm", "lbdrn_plane_encode", "lbdrn_plane_decode", "lbdrn_jp2k_encode", "lbdrn_train_step"}
     host_only = {"lbdrn_last_error", "lbdrn_abi_version", "lbdrn_device_check", "lbdrn_param_count", "lbdrn_feature_dim",
-                 "lbdrn_train_group_max", "lbdrn_train_step_features", "lbdrn_train_group_size", "lbdrn_train_profile_mode",
+                 "lbdrn_apply_instance", "lbdrn_train_group_max", "lbdrn_train_step_features", "lbdrn_train_group_size", "lbdrn_train_profile_mode",
                  "lbdrn_mt19937_jump_poly", "lbdrn_jp2k_block_count", "lbdrn_weights_encode", "lbdrn_weights_info", "lbdrn_weights_decode"}
     sizing = {n for n in _lib.SIGNATURES if n.endswith(("_workspace", "_bound", "_bytes"))}
     assert device_entries | host_only | sizing == set(_lib.SIGNATURES), set(_lib.SIGNATURES) ^ (device_entries | host_only | sizing)

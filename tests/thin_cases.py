@@ -124,21 +124,12 @@ def fused_apply_takes(C, D, P, F, bc, nl, act):
     """Whether LBDRN_PATH_MFMA has an apply kernel for this network on these features: make_plan (csrc/apply_mfma.hip: the
     weights of k_apply_mfma resident in 160 KB of LDS beside a one-row tile) or make_wapply_plan (csrc/apply_wide.inc: the
     streaming kernel, Sine, bc = 128 / 256, at most two hidden layers, a one-row tile in 64 KB).  Neither reads H or W: a
-    thin raster is refused exactly where a large one of the same bands and window is."""
-    ncolor = F - 2 * P
-    window = C * (1 + 2 * D) * (64 + 2 * D)
-    if bc in (32, 64, 128) and C <= 32:
-        NT, half = bc // 32, bc // 2
-        S0 = P + ((ncolor + 1) // 2 + 3) // 4 * 4
-        pack = S0 * 64 * NT + (nl - 1) * half * 64 * NT + half * 64 + nl * NT * 32 + 32 + 4
-        ktab = 2 * 2 * (S0 - P) + 2
-        if (pack + ktab + P + 64 * P + window) * 4 <= 160 * 1024:
-            return True
-    if act == "sine" and bc in (128, 256) and C <= 16 and nl <= 2 and ncolor >= 1:
-        o = 2 * ncolor + 2 + P + 64 * P
-        if (((o + 3) & ~3) + window) * 4 <= 64 * 1024:
-            return True
-    return False
+    thin raster is refused exactly where a large one of the same bands and window is.  The two planners are restated once, in
+    tests/apply_plan_reference.py: this is its `supported` for a table row (colours on; P = 0, 1 or 25)."""
+    import apply_plan_reference as R
+    s = R.Shape(C, D, bc, nl, act, coords=P > 0, embed=P > 1)
+    assert (s.P, s.F) == (P, F), (s, P, F)
+    return R.supported(s)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
