@@ -27,6 +27,13 @@ raster_io.write_raster(path, image, geo=tags), and one record says so (`Tags: <n
 copies FILE's tags verbatim and wins; `--no-tags` ignores the chunk; a .npy output gets none.  With `--out-overviews` and no
 `--out-nodata`, a stored GDAL_NODATA that is an integer sample value is the overviews' nodata.
 
+A file written with `encode.py --nodata V` carries a losslessly coded mask of its nodata samples between those two
+(container.unpack_nodata_trailer).  The mask step (lbdrn_hip.nodata.apply) is the last thing done to a tile's or a window
+piece's reconstruction, in HBM: V where the mask is set, and a valid sample that decodes to V moves one count off it -- so the
+raster equals V exactly where the original did.  One record says so (`Nodata: V=<V>`); `--no-mask` leaves the step out.  V is
+the overviews' nodata with `--out-overviews` unless `--out-nodata` names one (it wins over a stored GDAL_NODATA), and a TIFF
+output that gets no GDAL_NODATA from stored or copied tags gets one that names V.
+
 `-org ORG --metrics [--metrics-peak P] [--metrics-json FILE]` adds, behind the `PSNR:` / `Max error:` record, one `Quality band c:`
 line per band and one `Quality:` line for the raster (lbdrn_hip.quality.compare: error statistics, SSIM and the spectral angle,
 computed on the GPU).  The other records are what they are without the flag."""
@@ -40,7 +47,7 @@ import numpy as np
 import torch
 
 import logger
-from lbdrn_hip import codec, container, geotags, ops, raster_io, shard
+from lbdrn_hip import codec, container, geotags, nodata, ops, raster_io, shard
 from lbdrn_hip.features import FeatCfg
 from LBDRNdataset import tile_windows, write_tiff_with_gdal
 
@@ -53,11 +60,12 @@ def read_image_header(bitstream):
     return container.unpack_header(bitstream)
 
 
-def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=None, out=None, geo=None):
+def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=None, out=None, geo=None, mask=None):
     """Decode one image or tile from the front of `bitstream`; returns the remaining bytes
     (ref decode.py:56-141).  layer: the tile's residual body (LBR1), applied to the reconstruction in HBM.  out: the
     options of --out-compress (raster_io.write_raster_device); the raster is then written from the reconstruction where it
-    lies, without a host copy of it.  geo: the tags for a raster written without those options (write_plain)."""
+    lies, without a host copy of it.  geo: the tags for a raster written without those options (write_plain).  mask: (V, kind,
+    body) of the tile from the file's nodata chunk: the mask step, applied last, in HBM."""
     nn_payload, bitstream = bitstream[:nn_bytes], bitstream[nn_bytes:]
     base_payload, bitstream = bitstream[:base_bytes], bitstream[base_bytes:]
     base = container.decode_base(base_payload, device=DEVICE, keep_on_device=True)   # ref decode.py:69-73
@@ -73,15 +81,21 @@ def test(bitstream, dirname, filename, nn_bytes, base_bytes, write=True, layer=N
         rec = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE, keep_on_device=True)
         if layer is not None:
             rec = codec.residual_apply(layer, rec.contiguous())
+        if mask is not None:
+            rec = nodata.apply(rec.contiguous(), mask[1], mask[2], mask[0])
         raster_io.write_raster_device(recon_path, rec.contiguous(), **out)
         test.last_image = None
         logger.log.info(f"Recon: {recon_path}")
         return bitstream
-    if layer is None:
+    if layer is None and mask is None:
         image = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE)
     else:
-        rec = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE, keep_on_device=True)
-        image = ops.from_device_u16(codec.residual_apply(layer, rec.contiguous()))
+        rec = codec.apply_image(base, params, K, D, bc, nl, cfg=cfg, device=DEVICE, keep_on_device=True).contiguous()
+        if layer is not None:
+            rec = codec.residual_apply(layer, rec)
+        if mask is not None:
+            rec = nodata.apply(rec, mask[1], mask[2], mask[0])
+        image = ops.from_device_u16(rec)
     test.last_image = image
     if write:
         write_plain(recon_path, image, geo)
@@ -109,20 +123,38 @@ def stored_tags(args, bitstream, path, window=None):
     return tags if window is None else geotags.shift(tags, window[0], window[1])
 
 
-def out_options(args, geo=None):
+def stored_mask(args, bitstream):
+    """(V, [(kind, body) per tile]) of a file with a nodata chunk (encode.py --nodata); None without one and under --no-mask"""
+    return None if args.no_mask else container.unpack_nodata_trailer(bitstream)
+
+
+def with_nodata_tag(tags, V, path):
+    """`tags` (or None) with a GDAL_NODATA that names V added where they have none -- what a TIFF written from a masked
+    reconstruction carries; unchanged without a mask (V None) and for a .npy output"""
+    if V is None or path.endswith(".npy") or any(t[0] == geotags.GDAL_NODATA for t in tags or ()):
+        return tags
+    text = str(V).encode("ascii") + b"\0"
+    return sorted(list(tags or []) + [(geotags.GDAL_NODATA, 2, len(text), text)], key=lambda t: t[0])
+
+
+def out_options(args, geo=None, V=None, path=""):
     """the raster_io.write_raster_device options --out-compress / --out-tile / --out-overviews / --out-resampling / --out-nodata /
     --out-georef ask for; None: today's writer.  geo: the stored tags to restore (stored_tags): they ride the `geo` option,
-    and their GDAL_NODATA, where it is an integer sample value, is the overviews' nodata unless --out-nodata names one."""
+    and their GDAL_NODATA, where it is an integer sample value, is the overviews' nodata unless --out-nodata names one.  V: the
+    value of the file's nodata chunk where its mask is applied: it comes before the stored tag, and the tags written -- stored
+    or copied -- get a GDAL_NODATA that names it where they have none (with_nodata_tag)."""
     if args.out_compress is None:
         return None
     out = {"compress": args.out_compress, "tile": args.out_tile}
     if args.out_overviews is not None:
-        nodata = args.out_nodata if args.out_nodata is not None else geotags.stored_nodata(geo, 16)
-        out.update(overviews=args.out_overviews, resampling=args.out_resampling or "average", nodata=nodata)
+        value = args.out_nodata if args.out_nodata is not None else V if V is not None else geotags.stored_nodata(geo, 16)
+        out.update(overviews=args.out_overviews, resampling=args.out_resampling or "average", nodata=value)
     if args.out_georef is not None:
         out["geo"] = raster_io.read_geo_tags(args.out_georef) or None
     elif geo:
         out["geo"] = geo
+    if V is not None:
+        out["geo"] = with_nodata_tag(out.get("geo"), V, path)
     return out
 
 
@@ -177,10 +209,17 @@ def decode_window_main(args, rank, world):
         logger.log.info(f"Residual layer: max error {layer[0]}")
     # decode_window_pieces applies a layer by default; only --no-enhancement has anything to say to it
     more = {"enhance": False} if args.no_enhancement else {}
+    masks = stored_mask(args, bitstream)
+    V = masks[0] if masks is not None else None
+    if V is not None:
+        logger.log.info(f"Nodata: V={V}")
+    if args.no_mask:
+        more["mask"] = False
     _, parts = codec.decode_window_pieces(bitstream, args.window, device=DEVICE, take=lambda k, piece: k % world == rank, **more)
     recon_path = args.out_path or f"{dirname}/{basename[:-4]}_recon_x{x0}_y{y0}_w{w}_h{h}.tif"
     geo = stored_tags(args, bitstream, recon_path, (x0, y0, w, h))
-    out = out_options(args, geo)
+    out = out_options(args, geo, V, recon_path)
+    plain_geo = with_nodata_tag(geo, V, recon_path)
     on_device = out is not None and world == 1      # the pieces stay in HBM, are put together there and written from there
     if on_device:
         image = None
@@ -202,7 +241,7 @@ def decode_window_main(args, rank, world):
                 if image is None:
                     image = np.zeros((rec.shape[0], h, w), rec.dtype)
                 image[:, oy:oy + rec.shape[1], ox:ox + rec.shape[2]] = rec
-            write_merged(recon_path, image, out, geo)
+            write_merged(recon_path, image, out, plain_geo)
         logger.log.info(f"Recon: {recon_path}")
         if geo:
             logger.log.info(f"Tags: {len(geo)} tags restored")
@@ -230,6 +269,8 @@ def main(argv=None, shard_tiles=None):
                    help="with --window: where the raster goes (default <name>_recon_x{X0}_y{Y0}_w{W}_h{H}.tif)")
     p.add_argument("--no-enhancement", dest="no_enhancement", action="store_true",
                    help="ignore the residual layer of a file that has one: the base reconstruction")
+    p.add_argument("--no-mask", dest="no_mask", action="store_true",
+                   help="ignore the nodata mask of a file that has one (encode.py --nodata): the reconstruction without the mask step")
     p.add_argument("--out-compress", dest="out_compress", choices=["deflate"], default=None,
                    help="write the reconstruction as a tiled, Deflate-compressed TIFF (predictor 2), compressed on the GPU")
     p.add_argument("--out-tile", dest="out_tile", type=int, default=None, metavar="N",
@@ -325,15 +366,21 @@ def main(argv=None, shard_tiles=None):
     if layer is not None:
         logger.log.info(f"Residual layer: max error {layer[0]}")
     bodies = layer[1] if layer is not None else [None] * (split_ratio * split_ratio)
+    masks = stored_mask(args, bitstream)
+    V = masks[0] if masks is not None else None
+    if V is not None:
+        logger.log.info(f"Nodata: V={V}")
+    masks = [(V,) + entry for entry in masks[1]] if masks is not None else [None] * (split_ratio * split_ratio)
     recon_path = f"{dirname}/{basename[:-4]}_recon.tif"
     geo = stored_tags(args, bitstream, recon_path)
-    out = out_options(args, geo) if rank == 0 else None      # (rank 0 writes)
+    out = out_options(args, geo, V, recon_path) if rank == 0 else None      # (rank 0 writes)
+    plain_geo = with_nodata_tag(geo, V, recon_path)
     bitstream = bitstream[n_hdr:]
     if split_ratio > 1:
         decoded, offset = [], 0
         for t, (i, j, x0, y0, w, h) in enumerate(tile_windows(width, height, split_ratio)):
             if t % world == rank:
-                test(bitstream[offset:], dirname, f"tile_{i}_{j}", nn_list[t], base_list[t], write=False, layer=bodies[t])
+                test(bitstream[offset:], dirname, f"tile_{i}_{j}", nn_list[t], base_list[t], write=False, layer=bodies[t], mask=masks[t])
                 decoded.append((t, test.last_image))
             offset += nn_list[t] + base_list[t]
         gathered = shard.gather_to_root(decoded) if world > 1 else [decoded]
@@ -344,9 +391,9 @@ def main(argv=None, shard_tiles=None):
                 if merged is None:
                     merged = np.zeros((tiles[t].shape[0], height, width), tiles[t].dtype)
                 merged[:, y0:y0 + h, x0:x0 + w] = tiles[t]
-            write_merged(recon_path, merged, out, geo)
+            write_merged(recon_path, merged, out, plain_geo)
     elif rank == 0:
-        test(bitstream, dirname, filename, nn_list[0], base_list[0], layer=bodies[0], out=out, geo=geo)
+        test(bitstream, dirname, filename, nn_list[0], base_list[0], layer=bodies[0], out=out, geo=plain_geo, mask=masks[0])
     if rank == 0:
         if geo:
             logger.log.info(f"Tags: {len(geo)} tags restored")

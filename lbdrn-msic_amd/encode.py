@@ -4,6 +4,7 @@ fused HIP kernels (lbdrn_hip.codec.fit_image) instead of DataLoader + ignite + a
 
 Bitstream: header | for each tile (row-major): network payload | MSB payload   (ref encode.py:29-36)
            [| residual-layer trailer, with --max-error T: container.pack_residual_trailer]
+           [| nodata chunk, with --nodata V: container.pack_nodata_trailer (lbdrn_hip/nodata.py)]
            [| geo-tag chunk, with --keep-tags on a source that has tags: container.pack_geo_trailer]
 
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N encode.py ... -sr S` fits the S*S tiles of the
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 
 import logger
-from lbdrn_hip import codec, container, geotags, raster_io, shard
+from lbdrn_hip import codec, container, geotags, nodata, raster_io, shard
 from lbdrn_hip.features import FeatCfg
 from LBDRNdataset import tile_windows
 
@@ -133,14 +134,68 @@ def report_and_pack(args, res, base_ahead=None):
     return nn_payload, base_payload
 
 
-def residual_layer(args, res, tile, nn_payload):
+def residual_layer(args, res, tile, nn_payload, mask=None):
     """--max-error T: the tile's residual layer, coded in a closed loop against what the decoder will reconstruct from
-    `nn_payload` and verified before it is handed back (lbdrn_hip.codec.residual_encode) -> LBR1 body."""
+    `nn_payload` and verified before it is handed back (lbdrn_hip.codec.residual_encode) -> LBR1 body.  mask: the tile's
+    (kind, body, count) under --nodata; the loop then runs through the mask step and T bounds the chain's result."""
+    more = {} if mask is None else {"nodata": (args.nodata, mask[0], mask[1])}
     body, err = codec.residual_encode(res, args.max_error, tile, nn_payload, args.K, args.D, args.base_channel, args.num_layers,
-                                      cfg=FeatCfg.from_constants(), device=DEVICE)
+                                      cfg=FeatCfg.from_constants(), device=DEVICE, **more)
     logger.log.info(f"Max error: {err}")
     logger.log.info(f"Residual layer: {len(body)} bytes: bpsp={len(body) * 8 / res.n_subpixels}")
     return body
+
+
+def nodata_value(parser, args):
+    """--nodata V | tag -> args.nodata as the sample value (the attribute is absent without the flag, like `window`), before
+    anything is read, fitted or written: a number outside 0..65535, or `tag` on a scene whose GDAL_NODATA is missing or
+    names no integer sample value, ends the run here."""
+    text = getattr(args, "nodata", None)
+    if text is None:
+        return None
+    if str(text).strip().lower() == "tag":
+        V = geotags.stored_nodata(raster_io.read_geo_tags(args.path), 16)
+        if V is None:
+            parser.error(f"--nodata tag: {args.path} has no GDAL_NODATA tag that names an integer sample value (0..65535)")
+    else:
+        try:
+            V = nodata.check_value(int(str(text).strip()))
+        except ValueError:
+            parser.error(f"--nodata {text}: a sample value (0..65535), or `tag` for the scene's GDAL_NODATA")
+    args.nodata = V
+    return V
+
+
+def nodata_mask(args, tile):
+    """--nodata V: the tile's entry of the nodata chunk, formed on the device from the tile's planes -> (kind, body, count)
+    (lbdrn_hip.nodata.tile_mask).  It does not depend on K."""
+    from lbdrn_hip import ops
+    return nodata.tile_mask(ops.to_device_u16(codec._as_planes(tile), DEVICE), args.nodata)
+
+
+def nodata_layer(args, res, tile, nn_payload, mask):
+    """What --nodata adds to one tile behind report_and_pack: the residual layer through the mask step (with --max-error), or
+    the chain check alone (without); then the tile's `Nodata:` record -> the LBR1 body or None."""
+    if args.max_error is not None:
+        layer = residual_layer(args, res, tile, nn_payload, mask)
+    else:
+        layer = None
+        codec.nodata_verify(res, (args.nodata, mask[0], mask[1]), tile, nn_payload, args.K, args.D, args.base_channel,
+                            args.num_layers, cfg=FeatCfg.from_constants(), device=DEVICE)
+    logger.log.info(f"Nodata: V={args.nodata}, {mask[2]} samples, mask {len(mask[1])} bytes")
+    return layer
+
+
+def nodata_chunk(args, masks):
+    """the 'LBNT' chunk of a file's tiles (masks: (kind, body, count) in tile order) and the file's `Nodata:` record"""
+    chunk = container.pack_nodata_trailer(args.nodata, [(kind, body) for kind, body, _ in masks])
+    return chunk, f"Nodata: V={args.nodata}, {sum(m[2] for m in masks)} samples, mask {len(chunk)} bytes"
+
+
+def layer_tau(args):
+    """what the 'LBRT' trailer stores: T, or with --nodata the bound the bodies were quantised for (nodata.tau_for)"""
+    V = getattr(args, "nodata", None)
+    return args.max_error if V is None else nodata.tau_for(args.max_error, V)
 
 
 def train_tiles(args, tiles, draws):
@@ -194,6 +249,9 @@ def build_parser():
     p.add_argument("--keep-tags", dest="keep_tags", action="store_true", default=argparse.SUPPRESS,
                    help="carry the input's georeferencing and nodata tags in the .bin (moved to the window with --window): "
                         "decode.py puts them on its raster.  Default: the file the reference's reader expects, nothing behind it")
+    p.add_argument("--nodata", dest="nodata", type=str, default=argparse.SUPPRESS, metavar="V|tag",
+                   help="keep samples of this value exact: the decoded raster equals V exactly where the input does, whatever K "
+                        "and --max-error are (tag: the input's integer GDAL_NODATA).  Appends a losslessly coded mask to the .bin")
     return p
 
 
@@ -272,6 +330,7 @@ def main(argv=None, shard_tiles=None):
         parser.error(str(e))
     check_scene_window(parser, args)
     window = getattr(args, "window", None)
+    V = nodata_value(parser, args)
     rank, world = 0, 1
     if shard_tiles is None:
         shard_tiles = shard.env_world()[1] > 1
@@ -337,39 +396,47 @@ def main(argv=None, shard_tiles=None):
     if jobs and BASE_CODEC.lower() in ("jp2", "jpeg2000", "jp2openjpeg") and os.environ.get("LBDRN_JP2_AHEAD", "1") != "0":
         ahead = BasePayloadsAhead([tile for _, tile in jobs], args.K)
     results = train_tiles(args, jobs, [draws[t] for t in mine]) if jobs else []
-    fitted = []   # (tile index, nn payload, MSB payload, captured log records or None, residual body or None)
+    fitted = []   # (tile index, nn payload, MSB payload, captured log records or None, residual body or None[, mask entry])
     for k, (t, (path, tile), res) in enumerate(zip(mine, jobs, results)):
         args.path = path
         take = (lambda k=k: ahead.take(k)) if ahead is not None else None
+        mask = nodata_mask(args, tile) if V is not None else None
         if world > 1:
             with logger.capture() as lines:
                 logger.log.info(args)
                 nn, base = report_and_pack(args, res, take)
-                layer = residual_layer(args, res, tile, nn) if args.max_error is not None else None
+                layer = (nodata_layer(args, res, tile, nn, mask) if V is not None else
+                         residual_layer(args, res, tile, nn) if args.max_error is not None else None)
         else:
             lines = None
             logger.log.info(args)
             nn, base = report_and_pack(args, res, take)
-            layer = residual_layer(args, res, tile, nn) if args.max_error is not None else None
-        fitted.append((t, nn, base, lines, layer))
+            layer = (nodata_layer(args, res, tile, nn, mask) if V is not None else
+                     residual_layer(args, res, tile, nn) if args.max_error is not None else None)
+        fitted.append((t, nn, base, lines, layer) + ((mask,) if V is not None else ()))      # the mask travels beside the layer
     gathered = shard.gather_to_root(fitted) if world > 1 else [fitted]
     if rank == 0:
         tiles = sorted((rec for part in gathered for rec in part), key=lambda rec: rec[0])
         assert [rec[0] for rec in tiles] == list(range(len(windows)))
-        for _, _, _, lines, _ in tiles:
-            if lines is not None:
-                logger.replay(lines)
+        for rec in tiles:
+            if rec[3] is not None:
+                logger.replay(rec[3])
         header = container.pack_header(args.split_ratio, width, height, args.K, args.base_channel,
                                        args.num_layers, args.D, [len(rec[1]) for rec in tiles],
                                        [len(rec[2]) for rec in tiles], activation=FeatCfg.from_constants().activation)
         with open(bitstream_path, "wb") as f:
             f.write(header)
-            for _, nn, base, _, _ in tiles:
-                f.write(nn)
-                f.write(base)
+            for rec in tiles:
+                f.write(rec[1])
+                f.write(rec[2])
             if args.max_error is not None:      # behind everything the header lists: older readers stop before it
-                f.write(container.pack_residual_trailer(args.max_error, [rec[4] for rec in tiles]))
+                f.write(container.pack_residual_trailer(layer_tau(args), [rec[4] for rec in tiles]))
+            if V is not None:                   # --nodata: between the layer and the tags
+                chunk, nodata_record = nodata_chunk(args, [rec[5] for rec in tiles])
+                f.write(chunk)
             f.write(geo_chunk)                  # --keep-tags: the last thing in the file, behind the layer where there is one
+        if V is not None:
+            logger.log.info(nodata_record)
         if geo_record is not None:
             logger.log.info(geo_record)
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
@@ -412,6 +479,7 @@ def main_k_points(argv, Ks):
         parser.error(str(e))
     check_scene_window(parser, base)
     window = getattr(base, "window", None)
+    V = nodata_value(parser, base)
     if not base.randomness:
         torch.manual_seed(base.seed)
         np.random.seed(base.seed)
@@ -472,6 +540,7 @@ def main_k_points(argv, Ks):
             outcome[K] = e
         return outcome
     shared_seconds = (time.time() - start_time) / len(todo)
+    masks = {}      # --nodata: a tile's mask does not depend on K -- formed once, by the first point that gets there, shared by all
     for K in todo:
         a = point[K]
         t_point = time.time()
@@ -486,8 +555,11 @@ def main_k_points(argv, Ks):
                 res = results[(t, K)]
                 take = (lambda t=t, K=K: ahead[K].take(t)) if K in ahead else None
                 logger.log.info(a)
+                if V is not None and t not in masks:
+                    masks[t] = nodata_mask(a, tile)
                 nn, base_payload = report_and_pack(a, res, take)
-                layer = residual_layer(a, res, tile, nn) if a.max_error is not None else None
+                layer = (nodata_layer(a, res, tile, nn, masks[t]) if V is not None else
+                         residual_layer(a, res, tile, nn) if a.max_error is not None else None)
                 tiles_out.append((nn, base_payload, layer))
             header = container.pack_header(a.split_ratio, width, height, K, a.base_channel, a.num_layers, a.D,
                                            [len(rec[0]) for rec in tiles_out], [len(rec[1]) for rec in tiles_out],
@@ -498,8 +570,13 @@ def main_k_points(argv, Ks):
                     f.write(nn)
                     f.write(base_payload)
                 if a.max_error is not None:
-                    f.write(container.pack_residual_trailer(a.max_error, [rec[2] for rec in tiles_out]))
+                    f.write(container.pack_residual_trailer(layer_tau(a), [rec[2] for rec in tiles_out]))
+                if V is not None:
+                    chunk, nodata_record = nodata_chunk(a, [masks[t] for t in range(len(tiles))])
+                    f.write(chunk)
                 f.write(geo_chunk)
+            if V is not None:
+                logger.log.info(nodata_record)
             if geo_record is not None:
                 logger.log.info(geo_record)
             # this point's share of the reading and fitting all points did together, plus its own reporting and packing

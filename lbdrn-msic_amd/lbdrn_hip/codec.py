@@ -767,16 +767,9 @@ def apply_image(base, params, K, D, base_channel, num_layers, cfg=None, device="
 
 # ---------------------------------------------------------------- the residual layer (encode.py --max-error)
 
-def residual_encode(fit_result, tau, img, nn_payload, K, D, base_channel, num_layers, cfg=None, device="cuda:0",
-                    path=ops.PATH_AUTO):
-    """The residual layer of one fitted tile -> (LBR1 body, max |orig - recon'| as verified).
-
-    Closed loop: `recon` is what every decoder of this package will compute -- lbdrn_decode_fused on the MSB planes the fit
-    left in HBM with the weights AFTER their payload round trip (container.decode_weights of `nn_payload`, the bytes that go
-    into the file; never the fit's un-truncated parameters).  Decode is canonical arithmetic, bit-identical on the generic
-    and MFMA paths and on a window's crop, so the difference coded here is the difference the decoder will see.  Before
-    the body is handed back it is decoded into a copy of recon and the bound is checked on every sample."""
-    from . import container, resid
+def _closed_loop_recon(fit_result, img, nn_payload, K, D, base_channel, num_layers, cfg, device, path):
+    """(the original's planes in HBM, what every decoder of this package reconstructs from the fit's MSB planes and `nn_payload`)"""
+    from . import container
     cfg = cfg or FeatCfg.from_constants()
     dev = torch.device(device)
     msb_d = fit_result.msb_device
@@ -788,13 +781,52 @@ def residual_encode(fit_result, tau, img, nn_payload, K, D, base_channel, num_la
     net = ops.make_net(geom.F, base_channel, C, num_layers, cfg.act)
     params = container.decode_weights(nn_payload, expected=ops.param_count(net))
     p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
-    recon = ops.decode_fused(geom, net, msb_d, p, path=path).contiguous()
+    return orig_d, ops.decode_fused(geom, net, msb_d, p, path=path).contiguous()
+
+
+def residual_encode(fit_result, tau, img, nn_payload, K, D, base_channel, num_layers, cfg=None, device="cuda:0",
+                    path=ops.PATH_AUTO, nodata=None):
+    """The residual layer of one fitted tile -> (LBR1 body, max |orig - recon'| as verified).
+
+    Closed loop: `recon` is what every decoder of this package will compute -- lbdrn_decode_fused on the MSB planes the fit
+    left in HBM with the weights AFTER their payload round trip (container.decode_weights of `nn_payload`, the bytes that go
+    into the file; never the fit's un-truncated parameters).  Decode is canonical arithmetic, bit-identical on the generic
+    and MFMA paths and on a window's crop, so the difference coded here is the difference the decoder will see.  Before
+    the body is handed back it is decoded into a copy of recon and the bound is checked on every sample.
+
+    nodata = (V, kind, mask body) (encode.py --nodata; lbdrn_hip.nodata.tile_mask): `tau` is then the bound T asked of the
+    whole chain.  The body is quantised for nodata.tau_for(T, V) and coded against the original with its nodata samples
+    replaced by recon's (error 0); the check decodes the body, runs the mask step behind it and asserts both that the
+    result equals V exactly where the original does and the bound T.  Absent: as ever."""
+    from . import resid
+    orig_d, recon = _closed_loop_recon(fit_result, img, nn_payload, K, D, base_channel, num_layers, cfg, device, path)
+    if nodata is not None:
+        from . import nodata as nd
+        V, kind, mask_body = nodata
+        body = resid.encode(nd.merge_original(orig_d, recon, V), recon, nd.tau_for(tau, V))
+        check = nd.apply(resid.apply(body, recon.clone()), kind, mask_body, V)
+        try:
+            return body, nd.check(orig_d, check, V, tau)
+        except ValueError as e:
+            raise ops._lib.LbdrnError(str(e)) from None
     body = resid.encode(orig_d, recon, tau)
     check = resid.apply(body, recon.clone())
     err = int((orig_d.to(torch.int32) & 0xFFFF).sub_(check.to(torch.int32) & 0xFFFF).abs_().max().item())
     if err > tau:
         raise ops._lib.LbdrnError(f"residual layer: max error {err} after decoding the body, {tau} was asked for; no bitstream is written")
     return body, err
+
+
+def nodata_verify(fit_result, nodata, img, nn_payload, K, D, base_channel, num_layers, cfg=None, device="cuda:0", path=ops.PATH_AUTO):
+    """encode.py --nodata without --max-error: the decoder's chain (base reconstruction, mask step) on the device, and the
+    assertion that its result equals V exactly where the original does -> max |orig - result|.  nodata = (V, kind, mask body)."""
+    from . import nodata as nd
+    orig_d, recon = _closed_loop_recon(fit_result, img, nn_payload, K, D, base_channel, num_layers, cfg, device, path)
+    V, kind, mask_body = nodata
+    try:
+        return nd.check(orig_d, nd.apply(recon, kind, mask_body, V), V)
+    except ValueError as e:
+        raise ops._lib.LbdrnError(str(e)) from None
 
 
 def residual_apply(body, recon_d, rect=None):
@@ -844,12 +876,14 @@ def window_pieces(width, height, split_ratio, window, D):
     return pieces
 
 
-def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, take=None, enhance=True):
+def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, take=None, enhance=True, mask=True):
     """The pieces of decode_window(): -> (scene (width, height), [(WindowPiece, [C][yb-ya][xb-xa] device tensor), ...]).
     take(k, piece) -> bool: which of the touched tiles (k counts them in tile order) this caller decodes (decode.py deals
     them over its ranks); the others are skipped like the tiles the window does not touch.  enhance: a file with a
     residual layer has it applied to each piece through the layer's rectangle argument -- only the blocks the piece touches
-    are decoded -- and the result equals that crop of the whole enhanced decode; False gives the base reconstruction."""
+    are decoded -- and the result equals that crop of the whole enhanced decode; False gives the base reconstruction.
+    mask: a file with a nodata chunk (encode.py --nodata) has the mask step applied to each piece behind that
+    (lbdrn_hip.nodata.apply with the piece's rectangle); False leaves it out."""
     from . import container
     from .features import window_tables
     bitstream = bytes(bitstream) if not isinstance(bitstream, (bytes, memoryview)) else bitstream
@@ -861,6 +895,7 @@ def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO,
         cfg.activation = activation
     dev = torch.device(device)
     layer = container.unpack_residual_trailer(bitstream) if enhance else None
+    nodata = container.unpack_nodata_trailer(bitstream) if mask else None
     offsets = [n_hdr]
     for t in range(split_ratio * split_ratio):                         # a tile is reached without reading the ones before it
         offsets.append(offsets[-1] + nn_list[t] + base_list[t])
@@ -894,18 +929,21 @@ def decode_window_pieces(bitstream, window, device="cuda:0", path=ops.PATH_AUTO,
         rec = rec[:, pc.top:pc.top + pc.yb - pc.ya, pc.left:pc.left + pc.xb - pc.xa]
         if layer is not None:
             rec = residual_apply(layer[1][pc.tile], rec.contiguous(), (pc.xa, pc.ya, pc.xb - pc.xa, pc.yb - pc.ya))
+        if nodata is not None:
+            from . import nodata as nd
+            rec = nd.apply(rec.contiguous(), *nodata[1][pc.tile], nodata[0], (pc.xa, pc.ya, pc.xb - pc.xa, pc.yb - pc.ya))
         out.append((pc, rec))
     return (width, height), out
 
 
-def decode_window(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, keep_on_device=True, enhance=True):
+def decode_window(bitstream, window, device="cuda:0", path=ops.PATH_AUTO, cfg=None, keep_on_device=True, enhance=True, mask=True):
     """Reconstruct window = (x0, y0, w, h) (scene pixels) of the scene a .bin holds -> uint16 [C][h][w], bit-identical to
     that crop of the whole reconstruction (decode.py), as a device tensor (uint16 bits in int16 storage, like every plane
     here) or, with keep_on_device=False, as numpy.  Tiles the window does not touch are skipped by the byte sizes the header
     lists: no weight stream, no MSB payload and no kernel runs for them.  A touched tile's MSB payload is decoded whole
     and cropped with a margin of D (window_pieces); its maximum, K, D, the colour switches and the activation are the
     tile's, and with USE_COORDINATES the crop brings the tile's table rows and columns (features.window_tables)."""
-    _, parts = decode_window_pieces(bitstream, window, device, path, cfg, enhance=enhance)
+    _, parts = decode_window_pieces(bitstream, window, device, path, cfg, enhance=enhance, mask=mask)
     x0, y0, w, h = (int(v) for v in window)
     out = None
     for pc, rec in parts:

@@ -1,6 +1,6 @@
 """.bin container of the codec: header (a12) + per tile the network payload and the MSB payload (+ behind them, with
-encode.py --max-error, the residual-layer trailer: pack_residual_trailer; and last of all, with encode.py --keep-tags, the
-geo-tag chunk: pack_geo_trailer).
+encode.py --max-error, the residual-layer trailer: pack_residual_trailer; then, with encode.py --nodata, the nodata chunk:
+pack_nodata_trailer; and last of all, with encode.py --keep-tags, the geo-tag chunk: pack_geo_trailer).
 
 Header layout (ref encode.py:37-64, decode.py:25-53), big-endian:
   hdr_len:u8  split_ratio:u8  width:u16  height:u16  (K<<4)|D:u8  (log2(bc)<<4)|nl:u8
@@ -124,46 +124,112 @@ def pack_residual_trailer(tau, bodies):
 
 
 def _trailers(buf):
-    """((tau, bodies) or None, geo tags or None, where the file ends without the chunk) from everything behind the listed
-    payloads: nothing, a residual-layer trailer, a geo-tag chunk, or the trailer followed by exactly one chunk.  Anything
+    """((tau, bodies) or None, (V, [(kind, body) per tile]) or None, geo tags or None, where the file ends without the geo-tag
+    chunk) from everything behind the listed payloads: [LBRT] [LBNT] [LBGT], each at most once and in this order.  Anything
     else raises."""
     from . import geotags
     off = residual_trailer_offset(buf)
     if len(buf) == off:
-        return None, None, off
+        return None, None, None, off
     if len(buf) < off:
         raise ValueError(f"bitstream of {len(buf)} bytes is shorter than the {off} its header lists")
-    if bytes(buf[off:off + 4]) == GEO_TRAILER_MAGIC:      # no layer: the chunk fills the rest (a second one, an 'LBRT' or any
-        return None, geotags.unpack(buf[off:]), off       # byte behind it is a size that does not match)
     tiles = buf[1] * buf[1]
-    if len(buf) < off + 7 + 4 * tiles or bytes(buf[off:off + 4]) != RESID_TRAILER_MAGIC:
+    pos, layer, nodata = off, None, None
+    magic = bytes(buf[off:off + 4])
+    if magic not in (RESID_TRAILER_MAGIC, NODATA_TRAILER_MAGIC, GEO_TRAILER_MAGIC) or (
+            magic == RESID_TRAILER_MAGIC and len(buf) < off + 7 + 4 * tiles):
         raise ValueError(f"{len(buf) - off} bytes behind the listed payloads are not a residual-layer trailer")
-    version, tau = struct.unpack_from(">BH", buf, off + 4)
-    if version != RESID_TRAILER_VERSION:
-        raise ValueError(f"residual-layer trailer version {version}: written by a newer version of this package")
-    sizes = struct.unpack_from(f">{tiles}I", buf, off + 7)
-    pos = off + 7 + 4 * tiles
-    if pos + sum(sizes) > len(buf):
-        raise ValueError(f"residual-layer trailer lists {sum(sizes)} bytes of bodies, the file holds {len(buf) - pos}")
-    bodies = []
-    for n in sizes:
-        bodies.append(bytes(buf[pos:pos + n]))
-        pos += n
+    if magic == RESID_TRAILER_MAGIC:
+        version, tau = struct.unpack_from(">BH", buf, off + 4)
+        if version != RESID_TRAILER_VERSION:
+            raise ValueError(f"residual-layer trailer version {version}: written by a newer version of this package")
+        sizes = struct.unpack_from(f">{tiles}I", buf, off + 7)
+        pos = off + 7 + 4 * tiles
+        if pos + sum(sizes) > len(buf):
+            raise ValueError(f"residual-layer trailer lists {sum(sizes)} bytes of bodies, the file holds {len(buf) - pos}")
+        bodies = []
+        for n in sizes:
+            bodies.append(bytes(buf[pos:pos + n]))
+            pos += n
+        layer = (tau, bodies)
+    if bytes(buf[pos:pos + 4]) == NODATA_TRAILER_MAGIC:
+        nodata, pos = _nodata_chunk(buf, pos, tiles)
     if pos == len(buf):
-        return (tau, bodies), None, pos
-    try:
-        return (tau, bodies), geotags.unpack(buf[pos:]), pos
+        return layer, nodata, None, pos
+    try:      # (a second 'LBNT', an 'LBRT' behind one, any byte behind the chunk: a chunk whose size does not match)
+        return layer, nodata, geotags.unpack(buf[pos:]), pos
     except ValueError as e:
-        raise ValueError(f"residual-layer trailer lists {sum(sizes)} bytes of bodies, the file holds {len(buf) - pos + sum(sizes)}, "
-                         f"and what follows them is no geo-tag chunk ({e})") from None
+        raise ValueError(f"{len(buf) - pos} bytes behind the {'nodata chunk' if nodata else 'residual bodies' if layer else 'payloads'} "
+                         f"that the file lists are no geo-tag chunk ({e})") from None
 
 
 def unpack_residual_trailer(buf):
     """-> (tau, [LBR1 body per tile]) of a .bin with a residual layer, None for a file that ends behind its listed payloads.
     Anything else behind them -- another magic, a newer version, sizes that do not fill the file -- raises.  A geo-tag chunk
     (pack_geo_trailer) behind the bodies, or behind the payloads of a file without a layer, changes nothing: the result is
-    that of the file with the chunk cut off."""
+    that of the file with the chunk cut off.  Nor does a nodata chunk (pack_nodata_trailer) between the two."""
     return _trailers(buf)[0]
+
+
+# ---------------------------------------------------------------- nodata chunk (encode.py --nodata)
+
+NODATA_TRAILER_MAGIC = b"LBNT"
+NODATA_TRAILER_VERSION = 1
+NODATA_NONE, NODATA_ALL, NODATA_SHARED, NODATA_PER_BAND = 0, 1, 2, 3      # a tile's kind (lbdrn_hip/nodata.py)
+
+
+def pack_nodata_trailer(value, tiles):
+    """magic 'LBNT' | version u8 = 1 | reserved u8 = 0 | V u16 | per tile: kind u8, size u32 | the tiles' mask bodies in tile
+    order (big-endian, like 'LBRT').  tiles: [(kind, body)].  kind 0: no sample of the tile equals V, kind 1: every sample
+    does (both without a body); kind 2: one mask plane shared by all bands, kind 3: one per band -- the body is
+    encode_base(the 0/1 planes as uint16, codec="LBB2").  Place: behind the residual-layer trailer where there is one, in
+    front of the geo-tag chunk.  The header is untouched; readers that do not know the chunk refuse the file."""
+    if not 0 <= int(value) <= 65535:
+        raise OverflowError(f"nodata value {value} does not fit its field (0..65535)")
+    out = NODATA_TRAILER_MAGIC + struct.pack(">BBH", NODATA_TRAILER_VERSION, 0, int(value))
+    for kind, body in tiles:
+        if kind not in (NODATA_NONE, NODATA_ALL, NODATA_SHARED, NODATA_PER_BAND):
+            raise ValueError(f"nodata chunk: tile kind {kind}")
+        if (len(body) != 0) != (kind in (NODATA_SHARED, NODATA_PER_BAND)):
+            raise ValueError(f"nodata chunk: a body of {len(body)} bytes with tile kind {kind}")
+        if len(body) >= 1 << 32:
+            raise OverflowError(f"mask body of {len(body)} bytes does not fit 4 bytes")
+        out += struct.pack(">BI", kind, len(body))
+    return out + b"".join(bytes(body) for _, body in tiles)
+
+
+def _nodata_chunk(buf, off, tiles):
+    """the 'LBNT' chunk that starts at buf[off] -> ((V, [(kind, body)]), where it ends)"""
+    table = off + 8 + 5 * tiles
+    if len(buf) < table:
+        raise ValueError(f"nodata chunk: {len(buf) - off} bytes do not hold its table of {tiles} tiles")
+    version, reserved, value = struct.unpack_from(">BBH", buf, off + 4)
+    if version != NODATA_TRAILER_VERSION:
+        raise ValueError(f"nodata chunk version {version}: written by a newer version of this package")
+    if reserved:
+        raise ValueError(f"nodata chunk with reserved field {reserved:#x}: written by a newer version of this package")
+    entries = [struct.unpack_from(">BI", buf, off + 8 + 5 * t) for t in range(tiles)]
+    for kind, size in entries:
+        if kind > NODATA_PER_BAND:
+            raise ValueError(f"nodata chunk: tile kind {kind}: written by a newer version of this package")
+        if (size != 0) != (kind in (NODATA_SHARED, NODATA_PER_BAND)):
+            raise ValueError(f"nodata chunk: a body of {size} bytes with tile kind {kind}")
+    total = sum(size for _, size in entries)
+    if table + total > len(buf):
+        raise ValueError(f"nodata chunk lists {total} bytes of mask bodies, the file holds {len(buf) - table}")
+    out, pos = [], table
+    for kind, size in entries:
+        out.append((kind, bytes(buf[pos:pos + size])))
+        pos += size
+    return (value, out), pos
+
+
+def unpack_nodata_trailer(buf):
+    """-> (V, [(kind, mask body) per tile]) of a .bin written with encode.py --nodata, None for a file without the chunk.  What
+    unpack_residual_trailer refuses is refused here too; so are the chunk in front of a residual-layer trailer or behind the
+    geo-tag chunk, two chunks, another version, a non-zero reserved byte, a kind above 3, a body with kind 0 or 1 (or none with
+    kind 2 or 3) and sizes that overrun the file."""
+    return _trailers(buf)[1]
 
 
 # ---------------------------------------------------------------- geo-tag trailer (encode.py --keep-tags)
@@ -182,12 +248,12 @@ def pack_geo_trailer(tags):
 def unpack_geo_trailer(buf):
     """-> the tag list of a .bin that carries the chunk, None for a file without it.  What unpack_residual_trailer refuses
     is refused here too; so are a chunk in front of the residual-layer trailer, two chunks and any byte behind the chunk."""
-    return _trailers(buf)[1]
+    return _trailers(buf)[2]
 
 
 def strip_geo_trailer(buf):
-    """The file without its geo-tag chunk (a residual-layer trailer stays); a file without one as it is."""
-    return bytes(buf[:_trailers(buf)[2]])
+    """The file without its geo-tag chunk (a residual-layer trailer and a nodata chunk stay); a file without one as it is."""
+    return bytes(buf[:_trailers(buf)[3]])
 
 
 # ---------------------------------------------------------------- weights payload (a10)

@@ -19,7 +19,9 @@ fi
 if [ -n "${K_IN_FLIGHT}" ]; then set -- "$@" --k-in-flight "${K_IN_FLIGHT}"; fi
 # KEEP_TAGS=1 is sweep.py's --keep-tags: every .bin carries its image's georeferencing and nodata tags.
 if [ "${KEEP_TAGS:-0}" = "1" ]; then set -- "$@" --keep-tags; fi
-NPROC=$(( ${NGPU:-1} * ${PER_GPU:-2} ))
+# NODATA=V (a sample value, or `tag`) is sweep.py's --nodata V: every .bin keeps samples of that value exact.
+if [ -n "${NODATA}" ]; then set -- "$@" --nodata "${NODATA}"; fi
+NPROC=$((${NGPU:-1} * ${PER_GPU:-2} ))
 if [ "${PER_GPU:-2}" -gt 1 ]; then export LBDRN_DEVICE_SHARED="${LBDRN_DEVICE_SHARED:-1}" LBDRN_OVERLAP_EVAL="${LBDRN_OVERLAP_EVAL:-0}"; fi
 if [ "${NPROC}" -gt 1 ]; then
     exec python -m torch.distributed.run --nnodes=1 --nproc-per-node "${NPROC}" --master-addr 127.0.0.1 \

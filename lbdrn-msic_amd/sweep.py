@@ -52,6 +52,8 @@ def build_parser():
                    help="sweep this part of every image only (encode.py --window)")
     p.add_argument("--keep-tags", dest="keep_tags", action="store_true",
                    help="every .bin carries its image's georeferencing and nodata tags (encode.py --keep-tags)")
+    p.add_argument("--nodata", dest="nodata", type=str, default=None, metavar="V|tag",
+                   help="every .bin keeps samples of this value exact (encode.py --nodata; tag: each image's GDAL_NODATA)")
     p.add_argument("--summary", action="store_true", help="rank 0 writes the results CSV at the end")
     p.add_argument("--k-in-flight", dest="k_in_flight", type=int, default=1, metavar="N",
                    help="fit up to N of the K points of an image side by side on the GPU (encode.main_k_points); "
@@ -85,9 +87,10 @@ def points(a):
 
 
 def common_args(a):
-    return ["-D", str(a.D), "-bc", str(a.base_channel), "-nl", str(a.num_layers),
+    return (["-D", str(a.D), "-bc", str(a.base_channel), "-nl", str(a.num_layers),
             "-lr", a.lr, "-bs", str(a.batch_size), "-e", str(a.epochs), "-sr", str(a.split_ratio),
             "-prec", str(a.precision)] + window_args(a, "--window") + (["--keep-tags"] if getattr(a, "keep_tags", False) else [])
+            + (["--nodata", str(a.nodata)] if getattr(a, "nodata", None) is not None else []))
 
 
 def window_args(a, flag):
