@@ -202,6 +202,16 @@ int lbdrn_decode_fused(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t
  * (relative colours, no positional features, bc <= 64, D in 1..3, an even band count, g->msb_max <= 2047: any 16-bit image at
  * K >= 5) and is ignored elsewhere.  *sse within 1e-6 relative of the flagless call like LBDRN_EVAL_FAST (measured: DESIGN.md 10). */
 #define LBDRN_EVAL_X16 0x1000
+/* path may also carry LBDRN_EVAL_VALID (additive: the ABI version did not change with it): g->reserved then holds a NODATA
+ * value V, 0..65535 (anything else: LBDRN_E_ARG, before anything is launched), and *sse is the sum of (y - label)^2 over the
+ * samples with img != V only -- the ranking sum of a fit that steps the valid pixels of a collared scene (encode.py
+ * --nodata-fit valid).  A sample is left out by its own value, band by band; a skipped term is a term not added, so the
+ * summation tree, the fixed order and the any-grid guarantee are those of the flagless call (same bits with
+ * LBDRN_EVAL_BACKGROUND, on any stream, run to run), an image that holds no V gives the flagless sum bit for bit, and one
+ * that holds nothing else gives 0.0.  Every path and every instance takes the flag (LBDRN_EVAL_FAST / LBDRN_EVAL_X16 keep
+ * their 1e-6 against the canonical masked sum); it selects no instance and lbdrn_apply_instance ignores it.  The pass
+ * still walks every tile of the raster.  Without the flag g->reserved is not read. */
+#define LBDRN_EVAL_VALID 0x4000
 int lbdrn_eval_sse(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t *img,
                    const uint16_t *msb, const float *params, double *sse, void *workspace,
                    size_t workspace_bytes, int32_t path, void *stream);
@@ -209,7 +219,7 @@ int lbdrn_eval_sse(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t *im
 /* DIAGNOSTIC (tests/test_apply_plan_host.py, tests/test_gpu_apply_instances.py): which instance of the fused apply pass serves a
  * request, and on what plan -- host arithmetic only, no device needed, nothing launched; g and net pass the checks of the two entry points
  * (with P > 0 the tables are present; neither is read).  path_word is the `path` word of lbdrn_eval_sse (LBDRN_EVAL_FAST and LBDRN_EVAL_X16 are read,
- * LBDRN_EVAL_BACKGROUND changes the grid and no instance), or path | LBDRN_APPLY_DECODE for the request lbdrn_decode_fused
+ * LBDRN_EVAL_BACKGROUND changes the grid and no instance, LBDRN_EVAL_VALID is accepted and ignored), or path | LBDRN_APPLY_DECODE for the request lbdrn_decode_fused
  * makes.  The answer is what LBDRN_PATH_MFMA runs (and LBDRN_PATH_AUTO with it); where LBDRN_PATH_MFMA answers
  * LBDRN_E_UNSUPPORTED so does this, and out is left as it was.  out[0] family: 1 k_apply_mfma (weights resident in LDS), 2
  * k_apply_wide (weights streamed); out[1] NT: hidden tiles, bc / 32 (family 1) or bc / 16 (family 2); out[2] family 1: 1 for

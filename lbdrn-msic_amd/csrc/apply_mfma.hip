@@ -285,6 +285,7 @@ struct ApplyArgs {
     double* partial;      // EVAL: [nvirt]
     int nvirt;            // virtual workgroups: virtual workgroup v takes tiles v, v + nvirt, .. and owns partial[v]; a
                           // launch of fewer real workgroups walks them in turn -- same sums bit for bit on any grid
+    int nodata;           // EVAL (LBDRN_EVAL_VALID): samples of img equal to it add no term; -1, which no sample equals: none
     unsigned long long* stamps;  // diagnostic build (-DLBDRN_APPLY_STAMPS): [gridDim.x][8] cycle sums of wave 0
 };
 
@@ -747,7 +748,7 @@ __global__ void __launch_bounds__(APPLY_THREADS) k_apply_mfma(ApplyArgs A)
                         int base = (int)pre[r] << g.K;             // decode.py:134
                         A.out[(int64_t)ch * HW + pix] = (uint16_t)(base + (int)rr);
                         if (A.y_out) A.y_out[pix * C + ch] = yv;
-                    } else {
+                    } else if ((int)pre[r] != A.nodata) {   // (a nodata sample: a term not added)
                         float lab = (float)((int)pre[r] & lmask) / scale;
                         float d = yv - lab;
                         sse += (double)(d * d);
@@ -875,6 +876,7 @@ struct ApplyCall {   // what an entry point hands the driver
     uint16_t* out;   // DECODE
     float* y_out;    // DECODE, optional
     double* sse;     // EVAL
+    int nodata;      // EVAL: the sample value left out of the sum (LBDRN_EVAL_VALID), or -1
     void* ws;
     size_t ws_bytes;
     bool background;
@@ -919,7 +921,7 @@ template <class Args>
 static int run_pass(Args& A, const ApplyCall& c, int mode, const float* packed, double* partial,
                     int (*dispatch)(const Args&, int, int, hipStream_t, bool))
 {
-    A.g = c.g; A.net = c.net; A.packed = packed; A.msb = c.msb; A.img = c.img; A.out = c.out; A.y_out = c.y_out; A.partial = partial;
+    A.g = c.g; A.net = c.net; A.packed = packed; A.msb = c.msb; A.img = c.img; A.out = c.out; A.y_out = c.y_out; A.partial = partial; A.nodata = c.nodata;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess)
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1050,14 +1052,14 @@ static int run_apply(const ApplyCall& c, int mode)
 int mfma_decode(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* msb, const float* params,
                 uint16_t* out, float* y_out, void* ws, size_t ws_bytes, hipStream_t s)
 {
-    return run_apply({g, net, nullptr, msb, params, out, y_out, nullptr, ws, ws_bytes, false, s}, MODE_DECODE);
+    return run_apply({g, net, nullptr, msb, params, out, y_out, nullptr, -1, ws, ws_bytes, false, s}, MODE_DECODE);
 }
 
 int mfma_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                   const uint16_t* msb, const float* params, double* sse, void* ws, size_t ws_bytes,
-                  bool background, bool fast, bool x16, hipStream_t s)
+                  bool background, bool fast, bool x16, int nodata, hipStream_t s)
 {
-    return run_apply({g, net, img, msb, params, nullptr, nullptr, sse, ws, ws_bytes, background, s},
+    return run_apply({g, net, img, msb, params, nullptr, nullptr, sse, nodata, ws, ws_bytes, background, s},
                      fast ? (x16 ? MODE_EVAL_X16 : MODE_EVAL_FAST) : MODE_EVAL);
 }
 

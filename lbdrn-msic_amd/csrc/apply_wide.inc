@@ -138,6 +138,7 @@ struct WApplyArgs {
     float* y_out;         // DECODE, optional
     double* partial;      // EVAL: [nvirt]
     int nvirt;
+    int nodata;           // EVAL (LBDRN_EVAL_VALID): samples of img equal to it add no term; -1: none
     unsigned long long* stamps;  // diagnostic build (-DLBDRN_APPLY_STAMPS): [gridDim.x][8] cycle sums of wave 0
 };
 
@@ -389,7 +390,7 @@ __global__ void __launch_bounds__(WA_THREADS, 1) k_apply_wide(WApplyArgs A)
                             const int base = (int)pre[r] << g.K;           // decode.py:134
                             A.out[(int64_t)ch * HW + pix] = (uint16_t)(base + (int)rr);
                             if (A.y_out) A.y_out[pix * C + ch] = yv;
-                        } else {
+                        } else if ((int)pre[r] != A.nodata) {   // (a nodata sample: a term not added)
                             const float lab = (float)((int)pre[r] & lmask) / scale;
                             const float d = yv - lab;
                             sse += (double)(d * d);

@@ -299,7 +299,12 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
     LBDRN_ALIGNED(workspace, ALIGN_WORKSPACE);
     const bool background = (path & LBDRN_EVAL_BACKGROUND) != 0, fast = (path & LBDRN_EVAL_FAST) != 0;
     const bool x16 = fast && (path & LBDRN_EVAL_X16) != 0;
-    path &= ~(LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16);
+    // LBDRN_EVAL_VALID: g->reserved is the nodata value, read only with the flag; -1, which no 16-bit sample equals, otherwise
+    const bool valid = (path & LBDRN_EVAL_VALID) != 0;
+    LBDRN_REQUIRE(!valid || (g->reserved >= 0 && g->reserved <= 65535),
+                  "LBDRN_EVAL_VALID: g->reserved holds the nodata value, 0..65535, not %d", g->reserved);
+    const int nodata = valid ? g->reserved : -1;
+    path &= ~(LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16 | LBDRN_EVAL_VALID);
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
     const lbdrn_geom gl = launch_geom(*g);
@@ -314,8 +319,8 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
     if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
     if (use_mfma)
         return mfma_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, background, fast, x16,
-                             (hipStream_t)stream);
-    return generic_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, (hipStream_t)stream);
+                             nodata, (hipStream_t)stream);
+    return generic_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, nodata, (hipStream_t)stream);
 }
 
 int lbdrn_apply_instance(const lbdrn_geom* g, const lbdrn_net* net, int32_t path_word, int32_t* out)
@@ -327,7 +332,7 @@ int lbdrn_apply_instance(const lbdrn_geom* g, const lbdrn_net* net, int32_t path
     const bool decode = (path_word & LBDRN_APPLY_DECODE) != 0, fast = (path_word & LBDRN_EVAL_FAST) != 0;
     const bool x16 = fast && (path_word & LBDRN_EVAL_X16) != 0;
     LBDRN_REQUIRE(!(decode && fast), "LBDRN_APPLY_DECODE takes no evaluation flag");
-    const int32_t path = path_word & ~(LBDRN_APPLY_DECODE | LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16);
+    const int32_t path = path_word & ~(LBDRN_APPLY_DECODE | LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16 | LBDRN_EVAL_VALID);
     LBDRN_REQUIRE(path >= LBDRN_PATH_AUTO && path <= LBDRN_PATH_MFMA, "unknown path %d", path);
     // (the request as ApplyMode counts it: the decode pass, the canonical evaluation, the fast one, the exact-operand one)
     if (!mfma_apply_supported(*g, *net) || !mfma_apply_instance(launch_geom(*g), *net, decode ? 0 : fast ? (x16 ? 3 : 2) : 1, out)) {

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 import logger
-from lbdrn_hip import codec, container, geotags, nodata, raster_io, shard
+from lbdrn_hip import codec, container, geotags, nodata, raster_io, sampler, shard
 from lbdrn_hip.features import FeatCfg
 from LBDRNdataset import tile_windows
 
@@ -60,7 +60,7 @@ def train(args, img=None):
         img = raster_io.read_raster(args.path)
     res = codec.fit_image(img, args.K, args.D, args.base_channel, args.num_layers, args.lr,
                           args.batch_size, args.epochs, args.val_duration,
-                          cfg=FeatCfg.from_constants(), device=DEVICE, host_msb=False)
+                          cfg=FeatCfg.from_constants(), device=DEVICE, host_msb=False, nodata=fit_nodata(args))
     return report_and_pack(args, res)
 
 
@@ -166,6 +166,30 @@ def nodata_value(parser, args):
     return V
 
 
+def nodata_fit_mode(parser, args):
+    """--nodata-fit {all,valid}: `valid` fits and ranks on the valid pixels only and needs --nodata, which names the value.
+    (Both attributes are absent without their flags, like `window`: the records of such a run stay.)"""
+    mode = getattr(args, "nodata_fit", None)
+    if mode == "valid" and getattr(args, "nodata", None) is None:
+        parser.error("--nodata-fit valid needs --nodata V|tag: it names the value that marks a pixel as not to be fitted")
+    return mode
+
+
+def fit_nodata(args):
+    """what the fit functions get as `nodata`: V under --nodata-fit valid, else None (the fit steps every pixel)"""
+    return args.nodata if getattr(args, "nodata_fit", None) == "valid" else None
+
+
+def nodata_fit_record(n_valid, n_pixels, batch_size):
+    """the record --nodata-fit valid adds per tile"""
+    return f"Nodata fit: {n_valid} of {n_pixels} pixels, {sampler.steps_per_epoch(n_valid, batch_size)} steps per epoch"
+
+
+def report_nodata_fit(args, res, tile):
+    if fit_nodata(args) is not None:
+        logger.log.info(nodata_fit_record(res.n_valid, tile.shape[-2] * tile.shape[-1], args.batch_size))
+
+
 def nodata_mask(args, tile):
     """--nodata V: the tile's entry of the nodata chunk, formed on the device from the tile's planes -> (kind, body, count)
     (lbdrn_hip.nodata.tile_mask).  It does not depend on K."""
@@ -205,7 +229,7 @@ def train_tiles(args, tiles, draws):
     results = codec.fit_images([arr for _, arr in tiles], args.K, args.D, args.base_channel, args.num_layers,
                                args.lr, args.batch_size, args.epochs, args.val_duration,
                                cfg=FeatCfg.from_constants(), device=DEVICE, host_msb=False, draws=draws,
-                               in_flight=IN_FLIGHT)
+                               in_flight=IN_FLIGHT, nodata=fit_nodata(args))
     return results
 
 
@@ -215,7 +239,7 @@ def train_tiles_at(args, arrays, Ks, draws):
     exception that fit ended with."""
     return codec.fit_images(arrays, Ks, args.D, args.base_channel, args.num_layers, args.lr, args.batch_size, args.epochs,
                             args.val_duration, cfg=FeatCfg.from_constants(), device=DEVICE, host_msb=False, draws=draws,
-                            in_flight=IN_FLIGHT, errors="return")
+                            in_flight=IN_FLIGHT, errors="return", nodata=fit_nodata(args))
 
 
 def _host_msb(res):
@@ -252,6 +276,9 @@ def build_parser():
     p.add_argument("--nodata", dest="nodata", type=str, default=argparse.SUPPRESS, metavar="V|tag",
                    help="keep samples of this value exact: the decoded raster equals V exactly where the input does, whatever K "
                         "and --max-error are (tag: the input's integer GDAL_NODATA).  Appends a losslessly coded mask to the .bin")
+    p.add_argument("--nodata-fit", dest="nodata_fit", choices=("all", "valid"), default=argparse.SUPPRESS,
+                   help="with --nodata: `valid` trains and ranks the epochs on the valid pixels only (a pixel is void where all its "
+                        "bands equal V); `all` (default) fits every pixel.  The .bin format is the same either way")
     return p
 
 
@@ -331,6 +358,7 @@ def main(argv=None, shard_tiles=None):
     check_scene_window(parser, args)
     window = getattr(args, "window", None)
     V = nodata_value(parser, args)
+    nodata_fit_mode(parser, args)
     rank, world = 0, 1
     if shard_tiles is None:
         shard_tiles = shard.env_world()[1] > 1
@@ -405,12 +433,14 @@ def main(argv=None, shard_tiles=None):
             with logger.capture() as lines:
                 logger.log.info(args)
                 nn, base = report_and_pack(args, res, take)
+                report_nodata_fit(args, res, tile)
                 layer = (nodata_layer(args, res, tile, nn, mask) if V is not None else
                          residual_layer(args, res, tile, nn) if args.max_error is not None else None)
         else:
             lines = None
             logger.log.info(args)
             nn, base = report_and_pack(args, res, take)
+            report_nodata_fit(args, res, tile)
             layer = (nodata_layer(args, res, tile, nn, mask) if V is not None else
                      residual_layer(args, res, tile, nn) if args.max_error is not None else None)
         fitted.append((t, nn, base, lines, layer) + ((mask,) if V is not None else ()))      # the mask travels beside the layer
@@ -480,6 +510,7 @@ def main_k_points(argv, Ks):
     check_scene_window(parser, base)
     window = getattr(base, "window", None)
     V = nodata_value(parser, base)
+    nodata_fit_mode(parser, base)
     if not base.randomness:
         torch.manual_seed(base.seed)
         np.random.seed(base.seed)
@@ -558,6 +589,7 @@ def main_k_points(argv, Ks):
                 if V is not None and t not in masks:
                     masks[t] = nodata_mask(a, tile)
                 nn, base_payload = report_and_pack(a, res, take)
+                report_nodata_fit(a, res, tile)
                 layer = (nodata_layer(a, res, tile, nn, masks[t]) if V is not None else
                          residual_layer(a, res, tile, nn) if a.max_error is not None else None)
                 tiles_out.append((nn, base_payload, layer))

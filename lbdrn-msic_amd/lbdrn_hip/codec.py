@@ -17,7 +17,7 @@ import torch
 from . import ops
 from .features import FeatCfg
 from .model import LBDRNModel
-from .sampler import DevicePermutationStream, GPU_RANDPERM_MAX, draw_pass_seeds, epoch_plan
+from .sampler import DevicePermutationStream, GPU_RANDPERM_MAX, as_valid_pixels, draw_pass_seeds, epoch_plan, steps_per_epoch as steps_of
 
 
 def lr_schedule(lr, epochs):
@@ -72,6 +72,7 @@ class FitResult:
         self.n_feature = None
         self.channels = None
         self.n_subpixels = None
+        self.n_valid = None         # with nodata=: the valid pixels the fit stepped through (None: all of them)
         self.seconds = {}
 
 
@@ -88,6 +89,7 @@ class DeviceFit:
         self.evaluated = []
         self.losses = None
         self.epochs = 0
+        self.n_valid = None       # with nodata=: the valid pixels (sampler.ValidPixels.n); None: every pixel was stepped
 
 
 _RNG_LOCK = threading.Lock()   # the global torch CPU generator is one per process
@@ -314,7 +316,7 @@ def _eval_stream(dev, main):
 
 
 def fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration=1,
-               cfg=None, path=ops.PATH_AUTO, keep_losses=False, seed=None, draws=None, alone=True):
+               cfg=None, path=ops.PATH_AUTO, keep_losses=False, seed=None, draws=None, alone=True, nodata=None):
     """Fit one image that already sits in HBM (img_d: [C,H,W] uint16 bits in int16 storage), on the
     calling thread's current stream.
 
@@ -326,7 +328,14 @@ def fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
     is not touched at all.  `alone`: no other fit is in flight in this process -- its evaluation passes then run
     in the background of the next epoch's training where overlap_evaluation() allows it (below).  No host
     synchronisation happens inside except the scalar read of MSB.max() that sizes the normalisation
-    (ref LBDRNdataset.py:120)."""
+    (ref LBDRNdataset.py:120).
+    nodata: a sample value V, or the sampler.ValidPixels the caller formed for this raster (encode.py --nodata-fit valid).  The
+    fit then steps and ranks on the valid pixels only: the permutations are those of n_valid elements on the same training
+    seeds, epoch e steps valid_idx[perm_e] (a list of pixel indices: lbdrn_train_epoch's contract, no new kernel), an epoch has
+    ceil(n_valid / batch_size) steps, and the evaluation passes leave the nodata samples out (LBDRN_EVAL_VALID), their mean
+    taken over the samples that are not nodata.  One more host read: n_valid.  A raster without any sample equal to V gives
+    the fit it gives without the argument, bit for bit; one of nothing but V runs no step and no pass and returns the
+    parameters it started from."""
     cfg = cfg or FeatCfg.from_constants()
     out = DeviceFit()
     dev = img_d.device
@@ -346,16 +355,25 @@ def fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
             # model on the CPU first, like the reference (encode.py:71-77): consumes the global generator;
             # then every pass's sampler seed
             draws = draw_fit(geom.F, base_channel, C, num_layers, epochs, val_duration)
-    stream = DevicePermutationStream(N, epochs, val_duration, dev, train_seeds=draws.train_seeds)
+    vp = as_valid_pixels(img_d, nodata)
+    n_fit = N if vp is None else vp.n                      # the pixels an epoch steps through
+    out.n_valid = None if vp is None else vp.n
     net = ops.make_net(geom.F, base_channel, C, num_layers, cfg.act)
     params = draws.params.to(dev, copy=True).contiguous()      # (its own copy: the draws may serve other fits)
     if params.numel() != ops.param_count(net):
         raise ValueError("draws were made for another network shape")
+    steps_per_epoch = steps_of(n_fit, batch_size)
+    if n_fit == 0:     # nothing but nodata: the mask layer covers every sample, the parameters are the ones drawn
+        out.best_params, out.msb, out.msb_max, out.geom, out.net = params, msb_d, msb_max, geom, net
+        out.mse_log, out.epochs = torch.zeros((epochs, 2), dtype=torch.float32, device=dev), epochs
+        out.losses = torch.zeros((epochs, 0), dtype=torch.float32, device=dev) if keep_losses else None
+        return out
+    stream = DevicePermutationStream(n_fit, epochs, val_duration, dev, train_seeds=draws.train_seeds)
     draws_params0 = params.clone()
     exp_avg = torch.zeros_like(params)
     exp_avg_sq = torch.zeros_like(params)
     lrs = lr_schedule(lr, epochs)
-    steps_per_epoch = (N + batch_size - 1) // batch_size
+    mean_over = float(N * C) if vp is None else vp.samples.to(torch.float64)   # (no nodata sample: N * C, the same bits)
     losses = torch.zeros((epochs, steps_per_epoch), dtype=torch.float32, device=dev) if keep_losses else None
     train_ws = ops.TrainWorkspace(geom, net, batch_size, dev).prepare(img_d, msb_d, path)   # a2-a4
     apply_ws = ops.ApplyWorkspace(geom, net, dev)
@@ -374,19 +392,21 @@ def fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
         side.wait_stream(main)       # the workspaces and the planes above are ready
     adam_steps = 0
     # (the first background pass and the steps beside it are timed with events nobody waits for: _calibrated_head)
-    hkey = _head_key(dev, net, N, batch_size)
+    hkey = _head_key(dev, net, n_fit, batch_size)
     cal_epoch = eval_epochs[0] if eval_epochs else 0
     cal_events = [torch.cuda.Event(enable_timing=True) for _ in range(4)] if (side is not None and alone and cal_epoch + 1 <= epochs) else None
     try:
         for e in range(1, epochs + 1):
             perm = stream.get(e).to(dev, non_blocking=True)                  # a4 (already on the device)
+            if vp is not None:
+                perm = vp.gather(perm)
             # While the previous epoch's evaluation pass runs in the background it holds half of the CUs: the steps beside
             # it go out WITHOUT the alone hint -- the half-chip launch that fits on the other half (k_train_stream) --, the
             # rest of the epoch with it (k_train_split, every CU).  Same numbers either way (lbdrn_hip.h: the hint
             # changes no bit), so where the line is drawn is a matter of time only.
             head = 0
             if side is not None and alone and e - 1 in eval_epochs:
-                head = background_steps(steps_per_epoch, net, N, batch_size)
+                head = background_steps(steps_per_epoch, net, n_fit, batch_size)
                 if "LBDRN_LONE_HEAD_FRAC" not in os.environ:
                     head = _calibrated_head(hkey, head, steps_per_epoch)
             for lo, hi, hint in ((0, head, False), (head, steps_per_epoch, alone)):
@@ -412,10 +432,11 @@ def fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
                     if cal_events is not None and e == cal_epoch:
                         cal_events[0].record()
                     sse = ops.eval_sse(geom, net, img_d, msb_d, snaps[k], path, apply_ws, background=background,
-                                       fast=fast_evaluation(), x16=exact16_evaluation())   # a9
+                                       fast=fast_evaluation(), x16=exact16_evaluation(),
+                                       nodata=None if vp is None else vp.value)   # a9
                     if cal_events is not None and e == cal_epoch:
                         cal_events[1].record()
-                    mses[k:k + 1].copy_((sse / float(N * C)).float())
+                    mses[k:k + 1].copy_((sse / mean_over).float())
                 out.evaluated.append(e)
     finally:
         if side is not None:       # whatever happened, the borrowed stream is joined before anybody else uses it
@@ -436,7 +457,7 @@ def fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
 
 
 def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration=1, cfg=None,
-              path=ops.PATH_AUTO, keep_losses=False, seed=None, draws=None):
+              path=ops.PATH_AUTO, keep_losses=False, seed=None, draws=None, nodata=None):
     """Several independent fits of ONE raster shape, stepping side by side on the calling thread's stream: every
     minibatch of the group is one launch (ops.train_epoch_group) -- two 8192-row minibatches are 256 workgroups,
     the whole chip, where two independent chains of 128-workgroup launches only meet by chance.  Each fit is exactly
@@ -448,10 +469,15 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
     FitDraws is only read here).  Fits that bring the same training seeds share ONE permutation stream: each epoch's
     permutation is generated once and the same device tensor is handed to all of them (lbdrn_hip.h: perm entries may
     alias, nothing writes through them).  The MSB plane, msb_max, the row matrix, the workspaces and the evaluation
-    pass (whether it qualifies for LBDRN_EVAL_X16 depends on that fit's msb_max) are every fit's own."""
+    pass (whether it qualifies for LBDRN_EVAL_X16 depends on that fit's msb_max) are every fit's own.
+    nodata: fit_device's argument, one for all fits or one entry per image.  The group call takes one minibatch count for all
+    its fits, so they must have ONE n_valid (fit_many splits where it differs); the K points of one raster -- one tensor
+    several times -- share one ValidPixels, and fits on the same training seeds still share each permutation: every fit
+    gathers its own valid_idx through it."""
     cfg = cfg or FeatCfg.from_constants()
     G = len(imgs_d)
     Ks = k_per_fit(K, G)
+    vps = valid_pixels_per_fit(imgs_d, nodata)
     dev = imgs_d[0].device
     C, H, W = imgs_d[0].shape
     if any(tuple(t.shape) != (C, H, W) for t in imgs_d):
@@ -459,6 +485,13 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
     N = H * W
     if N >= GPU_RANDPERM_MAX:
         raise ops._lib.LbdrnError(f"{N} pixels in one fit: split the image (-sr)")
+    if len({None if vp is None else vp.n for vp in vps}) > 1:
+        raise ValueError("the fits of a group must have one n_valid: " + ", ".join(str(None if vp is None else vp.n) for vp in vps))
+    n_fit = N if vps[0] is None else vps[0].n
+    if n_fit == 0:     # nothing but nodata in every raster: no step, no pass (fit_device)
+        return [fit_device(img_d, K_, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path, keep_losses,
+                           seed, draws[k] if draws is not None else None, alone=False, nodata=vp)
+                for k, (img_d, K_, vp) in enumerate(zip(imgs_d, Ks, vps))]
     outs = [DeviceFit() for _ in range(G)]
     st = []
     net = None
@@ -476,11 +509,13 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
         params = dr.params.to(dev, copy=True).contiguous()      # (its own copy: the draws may serve other fits)
         if params.numel() != ops.param_count(net):
             raise ValueError("draws were made for another network shape")
-        steps = (N + batch_size - 1) // batch_size
+        steps = steps_of(n_fit, batch_size)
         seeds = tuple(int(s_) for s_ in dr.train_seeds)
         if seeds not in streams:
-            streams[seeds] = DevicePermutationStream(N, epochs, val_duration, dev, train_seeds=seeds)
+            streams[seeds] = DevicePermutationStream(n_fit, epochs, val_duration, dev, train_seeds=seeds)
+        vp = vps[k]
         st.append(dict(
+            vp=vp, mean_over=float(N * C) if vp is None else vp.samples.to(torch.float64),
             img=img_d, msb=msb_d, msb_max=msb_max, geom=geom, params=params, params0=params.clone(),
             m=torch.zeros_like(params), v=torch.zeros_like(params),
             perms=streams[seeds],
@@ -488,7 +523,7 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
             tws=ops.TrainWorkspace(geom, net, batch_size, dev).prepare(img_d, msb_d, path),   # a2-a4
             aws=ops.ApplyWorkspace(geom, net, dev)))
     lrs = lr_schedule(lr, epochs)
-    steps_per_epoch = (N + batch_size - 1) // batch_size
+    steps_per_epoch = steps_of(n_fit, batch_size)
     eval_epochs = [] if epochs == 1 else [e for e in range(1, epochs + 1) if e % min(val_duration, epochs) == 0]
     for f in st:
         f["snaps"] = torch.empty((max(len(eval_epochs), 1), f["params"].numel()), dtype=torch.float32, device=dev)
@@ -496,7 +531,14 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
     adam_steps = 0
     for e in range(1, epochs + 1):
         of_stream = {id(ps): ps.get(e).to(dev, non_blocking=True) for ps in streams.values()}          # a4
-        perms = [of_stream[id(f["perms"])] for f in st]
+        gathered = {}    # (permutation stream, ValidPixels) -> valid_idx[perm], made once for the fits that share both
+        perms = []
+        for f in st:
+            key = (id(f["perms"]), id(f["vp"]))
+            if key not in gathered:
+                perm = of_stream[id(f["perms"])]
+                gathered[key] = perm if f["vp"] is None else f["vp"].gather(perm)
+            perms.append(gathered[key])
         ops.train_epoch_group([f["geom"] for f in st], net, [f["img"] for f in st], [f["msb"] for f in st], perms,
                               batch_size, [f["params"] for f in st], [f["m"] for f in st], [f["v"] for f in st],
                               adam_steps, lrs[e - 1], [f["losses"][e - 1] for f in st] if keep_losses else None,
@@ -506,8 +548,9 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
             k = eval_epochs.index(e)
             for f, out in zip(st, outs):
                 f["snaps"][k].copy_(f["params"])
-                sse = ops.eval_sse(f["geom"], net, f["img"], f["msb"], f["snaps"][k], path, f["aws"], fast=fast_evaluation(), x16=exact16_evaluation())   # a9
-                f["mses"][k:k + 1].copy_((sse / float(N * C)).float())
+                sse = ops.eval_sse(f["geom"], net, f["img"], f["msb"], f["snaps"][k], path, f["aws"], fast=fast_evaluation(), x16=exact16_evaluation(),
+                                   nodata=None if f["vp"] is None else f["vp"].value)   # a9
+                f["mses"][k:k + 1].copy_((sse / f["mean_over"]).float())
                 out.evaluated.append(e)
     for f, out in zip(st, outs):
         best_params = f["params"].clone() if epochs == 1 else f["params0"]      # encode.py:100-103 / :91
@@ -522,13 +565,14 @@ def fit_group(imgs_d, K, D, base_channel, num_layers, lr, batch_size, epochs, va
             mse_log[e - 1, 1] = improved[0].float()
         out.best_params, out.msb, out.msb_max, out.geom, out.net = best_params, f["msb"], f["msb_max"], f["geom"], net
         out.mse_log, out.losses, out.epochs = mse_log, f["losses"], epochs
+        out.n_valid = None if f["vp"] is None else f["vp"].n
     for ps in streams.values():
         ps.close()
     return outs
 
 
 def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration=1, cfg=None,
-             path=ops.PATH_AUTO, seed=19920517, in_flight=None, then=None, draws=None, group=None):
+             path=ops.PATH_AUTO, seed=19920517, in_flight=None, then=None, draws=None, group=None, nodata=None):
     """Fit several HBM-resident images on ONE GPU with `in_flight` of them progressing at a time (None: default_in_flight of
     the shape -- 4, or 3 at bc >= 128 --, cut to what the free memory holds); returns
     [then(fit) or fit, ...] in input order.
@@ -553,8 +597,12 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
     K: one int, or one K per image.  With a list, `images` may name one device tensor several times (the K points of one
     raster: counted once against the free memory) and `draws` one FitDraws several times (read-only); consecutive
     entries of one raster shape form a group whatever their K, and a group whose fits bring the same training seeds
-    generates each permutation once (fit_group)."""
+    generates each permutation once (fit_group).
+    nodata: fit_device's argument, one V for all images or one entry per image (a value, a ValidPixels, or None).  The valid
+    pixels are formed here, once per raster and value, before the jobs are: a group takes one n_valid, so tiles whose n_valid
+    differ fit on streams of their own, as tiles of different shapes do."""
     Ks = k_per_fit(K, len(images))
+    vps = valid_pixels_per_fit(images, nodata)
     K = Ks[0] if Ks else K
     if in_flight is None:
         in_flight = default_in_flight(*tuple(images[0].shape), K, D, base_channel, num_layers, cfg, path) if images else 4
@@ -593,10 +641,10 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
         with torch.cuda.stream(local.stream):
             if len(imgs) == 1:
                 fits = [fit_device(imgs[0], ks[0], D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg,
-                                   path, seed=seed, draws=drs[0], alone=False)]
+                                   path, seed=seed, draws=drs[0], alone=False, nodata=vps[idx[0]])]
             else:
                 fits = fit_group(imgs, ks, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
-                                 seed=seed, draws=drs if draws is not None else None)
+                                 seed=seed, draws=drs if draws is not None else None, nodata=[vps[i] for i in idx])
             outs = [then(fit) if then is not None else fit for fit in fits]
             done = torch.cuda.Event()
             done.record(local.stream)
@@ -605,16 +653,17 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
     drs_all = draws if draws is not None else [None] * len(images)
     if in_flight <= 1 or len(images) <= 1:
         results = []
-        for img_d, dr, k_ in zip(images, drs_all, Ks):
+        for img_d, dr, k_, vp in zip(images, drs_all, Ks, vps):
             fit = fit_device(img_d, k_, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
-                             seed=seed, draws=dr)
+                             seed=seed, draws=dr, nodata=vp)
             results.append(then(fit) if then is not None else fit)
         return results
-    jobs = form_jobs(images, drs_all, Ks, group)
+    n_valid = [None if vp is None else vp.n for vp in vps]
+    jobs = form_jobs(images, drs_all, Ks, group, n_valid)
     if group > 1 and 2 * sum(len(j[0]) for j in jobs if len(j[0]) > 1) < len(images):
         # mostly odd ones out (tiles of many shapes): groups would only halve the number of chains
         group = 1
-        jobs = form_jobs(images, drs_all, Ks, 1)
+        jobs = form_jobs(images, drs_all, Ks, 1, n_valid)
     with ThreadPoolExecutor(max_workers=max(1, in_flight // group)) as pool:
         done_jobs = list(pool.map(work, jobs))
     results = [None] * len(images)
@@ -625,13 +674,37 @@ def fit_many(images, K, D, base_channel, num_layers, lr, batch_size, epochs, val
     return results
 
 
-def form_jobs(images, draws, Ks, group):
+def valid_pixels_per_fit(images, nodata):
+    """`nodata` of fit_group / fit_many as one entry per image: None, or a sampler.ValidPixels.  One value is every image's;
+    a sequence brings one entry per image.  A raster named several times (the K points of a sweep) is looked at once per
+    value."""
+    if not isinstance(nodata, (list, tuple)):
+        nodata = [nodata] * len(images)
+    if len(nodata) != len(images):
+        raise ValueError(f"{len(nodata)} nodata entries for {len(images)} images: one, or one per image")
+    formed, out = {}, []
+    for img, nd in zip(images, nodata):
+        if nd is not None and not hasattr(nd, "idx"):
+            key = (id(img), int(nd))
+            if key not in formed:
+                formed[key] = as_valid_pixels(img, int(nd))
+            nd = formed[key]
+        out.append(nd)
+    return out
+
+
+def form_jobs(images, draws, Ks, group, n_valid=None):
     """fit_many's jobs: consecutive images of one raster shape, `group` at a time, whatever their K (the group call takes
-    what differs between the K points of a raster; a shape change splits) -> [(indices, images, draws, Ks), ...]."""
+    what differs between the K points of a raster; a shape change splits) -> [(indices, images, draws, Ks), ...].
+    n_valid (optional): one entry per image, the pixels its fit steps through under `nodata` (None: all of them); the group
+    call has one minibatch count for all its fits, so a change of it splits like a change of shape."""
+    if n_valid is None:
+        n_valid = [None] * len(images)
     jobs, k = [], 0
     while k < len(images):
         n = 1
-        while n < group and k + n < len(images) and tuple(images[k + n].shape) == tuple(images[k].shape):
+        while (n < group and k + n < len(images) and tuple(images[k + n].shape) == tuple(images[k].shape)
+               and n_valid[k + n] == n_valid[k]):
             n += 1
         jobs.append((list(range(k, k + n)), list(images[k:k + n]), list(draws[k:k + n]), list(Ks[k:k + n])))
         k += n
@@ -679,6 +752,7 @@ def _host_result(fit, epochs, seconds, host_msb):
     C, H, W = fit.msb.shape
     res.n_feature, res.channels, res.n_subpixels = fit.geom.F, C, H * W * C
     res.losses = fit.losses
+    res.n_valid = fit.n_valid
     return res
 
 
@@ -688,27 +762,29 @@ def _as_planes(img):
 
 
 def fit_image(img, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration=1, cfg=None,
-              device="cuda:0", path=ops.PATH_AUTO, keep_losses=False, host_msb=True, draws=None):
+              device="cuda:0", path=ops.PATH_AUTO, keep_losses=False, host_msb=True, draws=None, nodata=None):
     """Host-array front end of fit_device(): img numpy uint16 [C,H,W] or [H,W] -> FitResult.
-    host_msb=False leaves the MSB plane in HBM only (the encoder codes it there)."""
+    host_msb=False leaves the MSB plane in HBM only (the encoder codes it there).  nodata: fit_device's."""
     t0 = time.time()
     img_d = ops.to_device_u16(_as_planes(img), torch.device(device))
     t1 = time.time()
     fit = fit_device(img_d, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg,
-                     path, keep_losses, draws=draws)
+                     path, keep_losses, draws=draws, nodata=nodata)
     res = _host_result(fit, epochs, {"upload": t1 - t0}, host_msb)
     res.seconds["fit"] = time.time() - t1
     return res
 
 
 def fit_images(imgs, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration=1, cfg=None,
-               device="cuda:0", path=ops.PATH_AUTO, host_msb=True, draws=None, seed=None, in_flight=None, errors="raise"):
+               device="cuda:0", path=ops.PATH_AUTO, host_msb=True, draws=None, seed=None, in_flight=None, errors="raise",
+               nodata=None):
     """fit_image for several rasters with `in_flight` of them progressing at a time on the GPU (fit_many).
     Either every fit seeds itself (`seed`: independent images, one encode.py invocation each in the reference)
     or the caller brings the draws it made in order (`draws`: the tiles of one image, ref encode.py:231-262).
     K: one int, or one per entry; an array that appears several times in `imgs` (one tile at several K) is uploaded once.
     errors="return": a fit whose result cannot be taken to the host (_host_result: no epoch improved) is that entry's
-    exception in the list instead of ending the call -- the other points of a sweep finish."""
+    exception in the list instead of ending the call -- the other points of a sweep finish.
+    nodata: fit_many's (one value: the valid pixels of an array that appears several times are formed once)."""
     t0 = time.time()
     dev = torch.device(device)
     uploaded = {}
@@ -718,7 +794,7 @@ def fit_images(imgs, K, D, base_channel, num_layers, lr, batch_size, epochs, val
     tiles = [uploaded[id(img)] for img in imgs]
     t1 = time.time()
     fits = fit_many(tiles, K, D, base_channel, num_layers, lr, batch_size, epochs, val_duration, cfg, path,
-                    seed=seed, in_flight=in_flight, draws=draws)
+                    seed=seed, in_flight=in_flight, draws=draws, nodata=nodata)
     results = []
     for fit in fits:
         try:

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EVAL_BACKGROUND, EVAL_FAST, EVAL_X16, TRAIN_ALONE, Geom, Net, PATH_AUTO, check, lib
+from ._lib import EVAL_BACKGROUND, EVAL_FAST, EVAL_VALID, EVAL_X16, TRAIN_ALONE, Geom, Net, PATH_AUTO, check, lib
 
 
 def _call(fn, ref, *args):
@@ -181,8 +181,11 @@ def decode_fused(geom, net, msb, params, want_y=False, path=PATH_AUTO, ws=None):
     return (out, y) if want_y else out
 
 
-def eval_sse(geom, net, img, msb, params, path=PATH_AUTO, ws=None, out=None, background=False, fast=False, x16=False):
+def eval_sse(geom, net, img, msb, params, path=PATH_AUTO, ws=None, out=None, background=False, fast=False, x16=False,
+             nodata=None):
     """Whole-image sum of squared error as a device float64 scalar tensor (no sync).
+    nodata: a sample value V (0..65535); the sum then runs over the samples with img != V only (LBDRN_EVAL_VALID: the
+    value travels in a copy of the geometry's `reserved` field, the caller's struct is left as it is).
     background: launch on half as many workgroups (LBDRN_EVAL_BACKGROUND, lbdrn_hip.h); same sum bit for bit.
     fast: the epoch-ranking pass in the training step's arithmetic (LBDRN_EVAL_FAST: within 1e-6 relative of the
     canonical sum, a fifth less time); the default is the canonical arithmetic of the decode kernels.
@@ -193,10 +196,14 @@ def eval_sse(geom, net, img, msb, params, path=PATH_AUTO, ws=None, out=None, bac
     params = params.contiguous().float()
     sse = out if out is not None else torch.zeros(1, dtype=torch.float64, device=msb.device)
     ws = ws or ApplyWorkspace(geom, net, msb.device)
-    _call(lib().lbdrn_eval_sse, msb, ctypes.byref(geom.c), ctypes.byref(net), _ptr(img), _ptr(msb),
+    gc = geom.c
+    if nodata is not None:
+        gc = Geom.from_buffer_copy(geom.c)
+        gc.reserved = int(nodata)
+    _call(lib().lbdrn_eval_sse, msb, ctypes.byref(gc), ctypes.byref(net), _ptr(img), _ptr(msb),
                                _ptr(params), _ptr(sse), _ptr(ws.buf), ws.nbytes,
                                path | (EVAL_BACKGROUND if background else 0) | (EVAL_FAST if fast else 0) |
-                               (EVAL_X16 if (fast and x16) else 0))
+                               (EVAL_X16 if (fast and x16) else 0) | (EVAL_VALID if nodata is not None else 0))
     return sse
 
 

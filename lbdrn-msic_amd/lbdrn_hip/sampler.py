@@ -88,6 +88,55 @@ class DevicePermutationStream:
         self._batches = []
 
 
+class ValidPixels:
+    """The pixels a fit under `nodata=V` steps and ranks on (encode.py --nodata-fit valid).  A nodata SAMPLE is
+    img[c, y, x] == V; a VOID pixel is one whose C samples are all nodata; every other pixel is VALID -- also one that is
+    nodata in some bands only.
+        value      V
+        idx        the valid pixels in ascending raster order, int64, on the image's device
+        n          their count (the one host read forming them costs)
+        n_pixels   H * W
+        samples    device int64 scalar: the samples that are not nodata, what the ranking sum's mean divides by
+    One object serves every fit of the raster: the K points of a sweep share it (nothing writes through it)."""
+
+    def __init__(self, value, idx, n_pixels, samples):
+        self.value, self.idx, self.n, self.n_pixels, self.samples = int(value), idx, int(idx.numel()), int(n_pixels), samples
+
+    def steps_per_epoch(self, batch_size):
+        return steps_per_epoch(self.n, batch_size)
+
+    def gather(self, perm):
+        """Epoch order: perm is a permutation of range(n); a raster without a void pixel keeps it as it is."""
+        return perm if self.n == self.n_pixels else self.idx[perm]
+
+
+def steps_per_epoch(n, batch_size):
+    """Minibatches of one pass over n pixels, the last one short (no drop_last, ref encode.py:69); none for n = 0."""
+    return (int(n) + int(batch_size) - 1) // int(batch_size)
+
+
+def valid_pixels(img, value):
+    """ValidPixels of img ([C,H,W], uint16 bits in int16 or uint16 storage, or any integer dtype that holds the samples) for
+    the nodata value `value`, formed where the planes are: a compare, a reduction over the bands and one torch.nonzero, whose
+    result size is the only thing the host waits for."""
+    value = int(value)
+    if not 0 <= value <= 65535:
+        raise ValueError(f"nodata value {value} outside 0..65535")
+    if img.dtype == torch.uint16:
+        img = img.view(torch.int16)
+    v = value - 65536 if img.dtype == torch.int16 and value >= 32768 else value
+    nod = img == v
+    idx = torch.nonzero(~nod.all(dim=0).reshape(-1)).squeeze(1)
+    return ValidPixels(value, idx, img.shape[1] * img.shape[2], (~nod).sum())
+
+
+def as_valid_pixels(img, nodata):
+    """`nodata` of the fit functions: None, a value (formed here), or a ValidPixels the caller formed for this raster."""
+    if nodata is None or isinstance(nodata, ValidPixels):
+        return nodata
+    return valid_pixels(img, nodata)
+
+
 _SIDE = {}
 
 

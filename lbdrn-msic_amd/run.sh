@@ -21,6 +21,8 @@ if [ -n "${K_IN_FLIGHT}" ]; then set -- "$@" --k-in-flight "${K_IN_FLIGHT}"; fi
 if [ "${KEEP_TAGS:-0}" = "1" ]; then set -- "$@" --keep-tags; fi
 # NODATA=V (a sample value, or `tag`) is sweep.py's --nodata V: every .bin keeps samples of that value exact.
 if [ -n "${NODATA}" ]; then set -- "$@" --nodata "${NODATA}"; fi
+# NODATA_FIT=valid (with NODATA) is sweep.py's --nodata-fit valid: the fits step and rank on the valid pixels only.
+if [ -n "${NODATA_FIT}" ]; then set -- "$@" --nodata-fit "${NODATA_FIT}"; fi
 NPROC=$((${NGPU:-1} * ${PER_GPU:-2} ))
 if [ "${PER_GPU:-2}" -gt 1 ]; then export LBDRN_DEVICE_SHARED="${LBDRN_DEVICE_SHARED:-1}" LBDRN_OVERLAP_EVAL="${LBDRN_OVERLAP_EVAL:-0}"; fi
 if [ "${NPROC}" -gt 1 ]; then

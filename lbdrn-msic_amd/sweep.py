@@ -54,6 +54,8 @@ def build_parser():
                    help="every .bin carries its image's georeferencing and nodata tags (encode.py --keep-tags)")
     p.add_argument("--nodata", dest="nodata", type=str, default=None, metavar="V|tag",
                    help="every .bin keeps samples of this value exact (encode.py --nodata; tag: each image's GDAL_NODATA)")
+    p.add_argument("--nodata-fit", dest="nodata_fit", choices=("all", "valid"), default=None,
+                   help="with --nodata: `valid` fits and ranks on the valid pixels only (encode.py --nodata-fit)")
     p.add_argument("--summary", action="store_true", help="rank 0 writes the results CSV at the end")
     p.add_argument("--k-in-flight", dest="k_in_flight", type=int, default=1, metavar="N",
                    help="fit up to N of the K points of an image side by side on the GPU (encode.main_k_points); "
@@ -72,6 +74,8 @@ def parse(argv=None):
     a.images = a.images if a.images else list(REFERENCE_IMAGES)
     if a.k_in_flight < 1:
         raise SystemExit(f"--k-in-flight {a.k_in_flight}: 1 (point after point) or more")
+    if a.nodata_fit == "valid" and a.nodata is None:   # before any fit of the sweep starts, as encode.py refuses it
+        raise SystemExit("--nodata-fit valid needs --nodata V|tag")
     if os.environ.get("LBDRN_WEIGHTS_CODEC") != "fpzip":
         from lbdrn_hip import container
         try:   # before any fit of the sweep starts
@@ -90,7 +94,8 @@ def common_args(a):
     return (["-D", str(a.D), "-bc", str(a.base_channel), "-nl", str(a.num_layers),
             "-lr", a.lr, "-bs", str(a.batch_size), "-e", str(a.epochs), "-sr", str(a.split_ratio),
             "-prec", str(a.precision)] + window_args(a, "--window") + (["--keep-tags"] if getattr(a, "keep_tags", False) else [])
-            + (["--nodata", str(a.nodata)] if getattr(a, "nodata", None) is not None else []))
+            + (["--nodata", str(a.nodata)] if getattr(a, "nodata", None) is not None else [])
+            + (["--nodata-fit", a.nodata_fit] if getattr(a, "nodata_fit", None) is not None else []))
 
 
 def window_args(a, flag):
