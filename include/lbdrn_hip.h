@@ -212,6 +212,20 @@ int lbdrn_decode_fused(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t
  * their 1e-6 against the canonical masked sum); it selects no instance and lbdrn_apply_instance ignores it.  The pass
  * still walks every tile of the raster.  Without the flag g->reserved is not read. */
 #define LBDRN_EVAL_VALID 0x4000
+/* path may also carry LBDRN_EVAL_DECODED (additive: the ABI version did not change with it): *sse is then the CLOSED-LOOP sum,
+ * over all samples, of (img - out)^2, where out is exactly the uint16 lbdrn_decode_fused writes for the same (g, net, msb,
+ * params): out = (msb << K) + rint(y * (2^K - 1)), y from the canonical sigmoid -- the distortion of what every decoder will
+ * reconstruct from these weights, without a reconstructed raster.  The difference is taken literally, against the centre
+ * sample of msb: a plane that is not img >> K gives the sum a decode followed by a compare would give.  Every term is an
+ * integer below 2^32 and every accumulation is float64 (per-thread sums, the LDS tree, the per-workgroup partials, the sum of
+ * the partials), so *sse is the EXACT integer whenever the true sum is below 2^53 -- any raster of up to 2^31 samples at
+ * K <= 11 with msb = img >> K (terms below 2^22) -- and below that bound the summation order cannot matter: same value on
+ * either path, any grid (LBDRN_EVAL_BACKGROUND), any stream, run to run.  Decode arithmetic is canonical: with LBDRN_EVAL_FAST
+ * or LBDRN_EVAL_X16 the call returns LBDRN_E_ARG, and so does a NULL msb (both before the device is looked for).  With
+ * LBDRN_EVAL_VALID the sum runs over the samples with img != V, as there.  The canonical evaluation instance serves the call:
+ * the flag is a runtime argument, uniform over the launch, that selects no instance (lbdrn_apply_instance accepts and ignores
+ * it), and without it every path computes the bits it computed before. */
+#define LBDRN_EVAL_DECODED 0x8000
 int lbdrn_eval_sse(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t *img,
                    const uint16_t *msb, const float *params, double *sse, void *workspace,
                    size_t workspace_bytes, int32_t path, void *stream);
@@ -219,7 +233,7 @@ int lbdrn_eval_sse(const lbdrn_geom *g, const lbdrn_net *net, const uint16_t *im
 /* DIAGNOSTIC (tests/test_apply_plan_host.py, tests/test_gpu_apply_instances.py): which instance of the fused apply pass serves a
  * request, and on what plan -- host arithmetic only, no device needed, nothing launched; g and net pass the checks of the two entry points
  * (with P > 0 the tables are present; neither is read).  path_word is the `path` word of lbdrn_eval_sse (LBDRN_EVAL_FAST and LBDRN_EVAL_X16 are read,
- * LBDRN_EVAL_BACKGROUND changes the grid and no instance, LBDRN_EVAL_VALID is accepted and ignored), or path | LBDRN_APPLY_DECODE for the request lbdrn_decode_fused
+ * LBDRN_EVAL_BACKGROUND changes the grid and no instance, LBDRN_EVAL_VALID and LBDRN_EVAL_DECODED are accepted and ignored), or path | LBDRN_APPLY_DECODE for the request lbdrn_decode_fused
  * makes.  The answer is what LBDRN_PATH_MFMA runs (and LBDRN_PATH_AUTO with it); where LBDRN_PATH_MFMA answers
  * LBDRN_E_UNSUPPORTED so does this, and out is left as it was.  out[0] family: 1 k_apply_mfma (weights resident in LDS), 2
  * k_apply_wide (weights streamed); out[1] NT: hidden tiles, bc / 32 (family 1) or bc / 16 (family 2); out[2] family 1: 1 for

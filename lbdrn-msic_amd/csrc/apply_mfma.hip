@@ -286,11 +286,12 @@ struct ApplyArgs {
     int nvirt;            // virtual workgroups: virtual workgroup v takes tiles v, v + nvirt, .. and owns partial[v]; a
                           // launch of fewer real workgroups walks them in turn -- same sums bit for bit on any grid
     int nodata;           // EVAL (LBDRN_EVAL_VALID): samples of img equal to it add no term; -1, which no sample equals: none
+    int decoded;          // EVAL (LBDRN_EVAL_DECODED): a term is (img - out)^2, out the sample the decode pass writes; canonical instances only
     unsigned long long* stamps;  // diagnostic build (-DLBDRN_APPLY_STAMPS): [gridDim.x][8] cycle sums of wave 0
 };
 
 #ifdef LBDRN_APPLY_STAMPS
-#define ASTAMP(k)                                                                     \
+#define ASTAMP(k)                                                                    \
     do {                                                                              \
         unsigned long long t_;                                                        \
         __builtin_amdgcn_sched_barrier(0);                                            \
@@ -749,6 +750,14 @@ __global__ void __launch_bounds__(APPLY_THREADS) k_apply_mfma(ApplyArgs A)
                         A.out[(int64_t)ch * HW + pix] = (uint16_t)(base + (int)rr);
                         if (A.y_out) A.y_out[pix * C + ch] = yv;
                     } else if ((int)pre[r] != A.nodata) {   // (a nodata sample: a term not added)
+                        if (MODE == MODE_EVAL && A.decoded) {   // (uniform over the launch; the centre sample of msb, as the decode pass reads it)
+                            // (opaque: the band's 64-bit offset is formed here; left to the compiler, sixteen of them are held in
+                            //  registers over the loops -- 30 more VGPRs, which the flagless pass would pay too)
+                            int band = ch;
+                            asm volatile("" : "+v"(band));
+                            sse += decoded_term((int)pre[r], (int)A.msb[(int64_t)band * HW + pix], yv, scale, g.K);
+                            continue;
+                        }
                         float lab = (float)((int)pre[r] & lmask) / scale;
                         float d = yv - lab;
                         sse += (double)(d * d);
@@ -877,6 +886,7 @@ struct ApplyCall {   // what an entry point hands the driver
     float* y_out;    // DECODE, optional
     double* sse;     // EVAL
     int nodata;      // EVAL: the sample value left out of the sum (LBDRN_EVAL_VALID), or -1
+    bool decoded;    // EVAL: the closed-loop sum (LBDRN_EVAL_DECODED); the canonical instance serves it
     void* ws;
     size_t ws_bytes;
     bool background;
@@ -921,7 +931,7 @@ template <class Args>
 static int run_pass(Args& A, const ApplyCall& c, int mode, const float* packed, double* partial,
                     int (*dispatch)(const Args&, int, int, hipStream_t, bool))
 {
-    A.g = c.g; A.net = c.net; A.packed = packed; A.msb = c.msb; A.img = c.img; A.out = c.out; A.y_out = c.y_out; A.partial = partial; A.nodata = c.nodata;
+    A.g = c.g; A.net = c.net; A.packed = packed; A.msb = c.msb; A.img = c.img; A.out = c.out; A.y_out = c.y_out; A.partial = partial; A.nodata = c.nodata; A.decoded = c.decoded;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess)
         (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1052,14 +1062,14 @@ static int run_apply(const ApplyCall& c, int mode)
 int mfma_decode(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* msb, const float* params,
                 uint16_t* out, float* y_out, void* ws, size_t ws_bytes, hipStream_t s)
 {
-    return run_apply({g, net, nullptr, msb, params, out, y_out, nullptr, -1, ws, ws_bytes, false, s}, MODE_DECODE);
+    return run_apply({g, net, nullptr, msb, params, out, y_out, nullptr, -1, false, ws, ws_bytes, false, s}, MODE_DECODE);
 }
 
 int mfma_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                   const uint16_t* msb, const float* params, double* sse, void* ws, size_t ws_bytes,
-                  bool background, bool fast, bool x16, int nodata, hipStream_t s)
+                  bool background, bool fast, bool x16, int nodata, bool decoded, hipStream_t s)
 {
-    return run_apply({g, net, img, msb, params, nullptr, nullptr, sse, nodata, ws, ws_bytes, background, s},
+    return run_apply({g, net, img, msb, params, nullptr, nullptr, sse, nodata, decoded, ws, ws_bytes, background, s},
                      fast ? (x16 ? MODE_EVAL_X16 : MODE_EVAL_FAST) : MODE_EVAL);
 }
 

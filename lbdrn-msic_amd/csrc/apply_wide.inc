@@ -139,6 +139,7 @@ struct WApplyArgs {
     double* partial;      // EVAL: [nvirt]
     int nvirt;
     int nodata;           // EVAL (LBDRN_EVAL_VALID): samples of img equal to it add no term; -1: none
+    int decoded;          // EVAL (LBDRN_EVAL_DECODED): a term is (img - out)^2, out the sample the decode pass writes; canonical instance only
     unsigned long long* stamps;  // diagnostic build (-DLBDRN_APPLY_STAMPS): [gridDim.x][8] cycle sums of wave 0
 };
 
@@ -391,6 +392,12 @@ __global__ void __launch_bounds__(WA_THREADS, 1) k_apply_wide(WApplyArgs A)
                             A.out[(int64_t)ch * HW + pix] = (uint16_t)(base + (int)rr);
                             if (A.y_out) A.y_out[pix * C + ch] = yv;
                         } else if ((int)pre[r] != A.nodata) {   // (a nodata sample: a term not added)
+                            if (MODE == MODE_EVAL && A.decoded) {   // (uniform over the launch; the centre sample of msb, as the decode pass reads it)
+                                int band = ch;   // (opaque: the band's 64-bit offset is formed here, not held in registers over the loops: k_apply_mfma)
+                                asm volatile("" : "+v"(band));
+                                sse += decoded_term((int)pre[r], (int)A.msb[(int64_t)band * HW + pix], yv, scale, g.K);
+                                continue;
+                            }
                             const float lab = (float)((int)pre[r] & lmask) / scale;
                             const float d = yv - lab;
                             sse += (double)(d * d);

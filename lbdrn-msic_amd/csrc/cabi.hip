@@ -304,7 +304,12 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
     LBDRN_REQUIRE(!valid || (g->reserved >= 0 && g->reserved <= 65535),
                   "LBDRN_EVAL_VALID: g->reserved holds the nodata value, 0..65535, not %d", g->reserved);
     const int nodata = valid ? g->reserved : -1;
-    path &= ~(LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16 | LBDRN_EVAL_VALID);
+    // LBDRN_EVAL_DECODED: the closed-loop sum.  What a decoder reconstructs is canonical arithmetic on the plane it is given
+    const bool decoded = (path & LBDRN_EVAL_DECODED) != 0;
+    LBDRN_REQUIRE(!decoded || !(path & (LBDRN_EVAL_FAST | LBDRN_EVAL_X16)),
+                  "LBDRN_EVAL_DECODED takes neither LBDRN_EVAL_FAST nor LBDRN_EVAL_X16: decode arithmetic is canonical");
+    LBDRN_REQUIRE(!decoded || msb, "LBDRN_EVAL_DECODED: msb must not be null, it is the plane the reconstruction is built on");
+    path &= ~(LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16 | LBDRN_EVAL_VALID | LBDRN_EVAL_DECODED);
     bool use_mfma = false;
     if (int rc = pick_apply(g, net, path, &use_mfma)) return rc;
     const lbdrn_geom gl = launch_geom(*g);
@@ -319,8 +324,8 @@ int lbdrn_eval_sse(const lbdrn_geom* g, const lbdrn_net* net, const uint16_t* im
     if (int rc = workspace_fits("apply", workspace, workspace_bytes, lbdrn_apply_workspace(g, net))) return rc;
     if (use_mfma)
         return mfma_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, background, fast, x16,
-                             nodata, (hipStream_t)stream);
-    return generic_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, nodata, (hipStream_t)stream);
+                             nodata, decoded, (hipStream_t)stream);
+    return generic_eval_sse(gl, *net, img, msb, params, sse, workspace, workspace_bytes, nodata, decoded, (hipStream_t)stream);
 }
 
 int lbdrn_apply_instance(const lbdrn_geom* g, const lbdrn_net* net, int32_t path_word, int32_t* out)
@@ -332,7 +337,7 @@ int lbdrn_apply_instance(const lbdrn_geom* g, const lbdrn_net* net, int32_t path
     const bool decode = (path_word & LBDRN_APPLY_DECODE) != 0, fast = (path_word & LBDRN_EVAL_FAST) != 0;
     const bool x16 = fast && (path_word & LBDRN_EVAL_X16) != 0;
     LBDRN_REQUIRE(!(decode && fast), "LBDRN_APPLY_DECODE takes no evaluation flag");
-    const int32_t path = path_word & ~(LBDRN_APPLY_DECODE | LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16 | LBDRN_EVAL_VALID);
+    const int32_t path = path_word & ~(LBDRN_APPLY_DECODE | LBDRN_EVAL_BACKGROUND | LBDRN_EVAL_FAST | LBDRN_EVAL_X16 | LBDRN_EVAL_VALID | LBDRN_EVAL_DECODED);
     LBDRN_REQUIRE(path >= LBDRN_PATH_AUTO && path <= LBDRN_PATH_MFMA, "unknown path %d", path);
     // (the request as ApplyMode counts it: the decode pass, the canonical evaluation, the fast one, the exact-operand one)
     if (!mfma_apply_supported(*g, *net) || !mfma_apply_instance(launch_geom(*g), *net, decode ? 0 : fast ? (x16 ? 3 : 2) : 1, out)) {

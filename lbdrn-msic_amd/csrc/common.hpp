@@ -97,7 +97,7 @@ int generic_decode(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* ms
                    hipStream_t s);
 int generic_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                      const uint16_t* msb, const float* params, double* sse, void* ws,
-                     size_t ws_bytes, int nodata, hipStream_t s);   // nodata: LBDRN_EVAL_VALID's sample value, or -1
+                     size_t ws_bytes, int nodata, bool decoded, hipStream_t s);   // nodata: LBDRN_EVAL_VALID's sample value, or -1; decoded: LBDRN_EVAL_DECODED
 size_t generic_train_workspace(const lbdrn_net& net, int B);
 int generic_train_step(const lbdrn_net& net, const float* x, const float* t, int B, float* params,
                        float* m, float* v, int64_t adam_step, double lr, int apply_adam,
@@ -121,7 +121,7 @@ int mfma_decode(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* msb, 
                 uint16_t* out, float* y_out, void* ws, size_t ws_bytes, hipStream_t s);
 int mfma_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                   const uint16_t* msb, const float* params, double* sse, void* ws, size_t ws_bytes,
-                  bool background, bool fast, bool x16, int nodata, hipStream_t s);
+                  bool background, bool fast, bool x16, int nodata, bool decoded, hipStream_t s);   // decoded: LBDRN_EVAL_DECODED, never with fast
 // whether the instance that serves this evaluation request reads msb (host arithmetic; false: it takes img >> K)
 bool mfma_eval_reads_msb(const lbdrn_geom& g, const lbdrn_net& net, bool fast, bool x16);
 // which instance serves a request (0 decode, 1 evaluation, 2 fast, 3 exact-operand) and on what plan: lbdrn_apply_instance's out[8]

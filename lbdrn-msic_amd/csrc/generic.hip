@@ -442,10 +442,11 @@ __global__ void __launch_bounds__(256)
 
 constexpr int SSE_BLOCKS = 256;
 
-// partial[b] = sum over this block's strided elements of (y - label)^2 in float64
+// partial[b] = sum over this block's strided elements of (y - label)^2 in float64; with msb_dec (LBDRN_EVAL_DECODED: the MSB
+// plane, else NULL) of (img - out)^2, out the sample k_reconstruct writes
 __global__ void __launch_bounds__(256)
-    k_sse_partial(const float* __restrict__ y, const uint16_t* __restrict__ img, int C, int64_t HW,
-                  int64_t first, int64_t n, int K, int nodata, double* __restrict__ partial)
+    k_sse_partial(const float* __restrict__ y, const uint16_t* __restrict__ img, const uint16_t* __restrict__ msb_dec, int C,
+                  int64_t HW, int64_t first, int64_t n, int K, int nodata, double* __restrict__ partial)
 {
     const float denom = (float)((1 << K) - 1);
     const int mask = (1 << K) - 1;
@@ -456,6 +457,10 @@ __global__ void __launch_bounds__(256)
         int c = (int)(e - i * C);
         const int v = (int)img[(int64_t)c * HW + first + i];
         if (v == nodata) continue;   // LBDRN_EVAL_VALID: a nodata sample is a term not added (-1: no sample equals it)
+        if (msb_dec) {
+            acc += decoded_term(v, (int)msb_dec[(int64_t)c * HW + first + i], y[e], denom, K);
+            continue;
+        }
         float lab = (float)(v & mask) / denom;
         float d = y[e] - lab;
         acc += (double)(d * d);
@@ -538,7 +543,7 @@ int generic_decode(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* ms
 
 int generic_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* img,
                      const uint16_t* msb, const float* params, double* sse, void* ws,
-                     size_t ws_bytes, int nodata, hipStream_t s)
+                     size_t ws_bytes, int nodata, bool decoded, hipStream_t s)
 {
     ApplyWs a;
     if (int rc = carve_apply(g, net, ws, ws_bytes, &a)) return rc;
@@ -547,7 +552,7 @@ int generic_eval_sse(const lbdrn_geom& g, const lbdrn_net& net, const uint16_t* 
         int64_t n = std::min(a.chunk, HW - first);
         if (int rc = generic_features(g, msb, nullptr, n, first, a.x, s)) return rc;
         if (int rc = generic_forward(net, params, a.x, n, a.y, a.fwd, a.fwd_bytes, s)) return rc;
-        k_sse_partial<<<SSE_BLOCKS, 256, 0, s>>>(a.y, img, net.C, HW, first, n, g.K, nodata, a.partial);
+        k_sse_partial<<<SSE_BLOCKS, 256, 0, s>>>(a.y, img, decoded ? msb : nullptr, net.C, HW, first, n, g.K, nodata, a.partial);
         LBDRN_LAUNCH_CHECK();
         k_sum_partials<<<1, 64, 0, s>>>(a.partial, SSE_BLOCKS, first != 0, sse);
         LBDRN_LAUNCH_CHECK();

@@ -116,6 +116,16 @@ LBDRN_DEV float canon_sigmoid(float z)
     return (z >= 0.0f) ? 1.0f / d : t / d;  // IEEE division (-fhip-fp32-correctly-rounded-divide-sqrt)
 }
 
+// LBDRN_EVAL_DECODED: one term of the closed-loop sum, (img - out)^2 with out the uint16 the decode passes store for this
+// sample -- (msb << K) + torch.round(y * (2^K - 1)), decode.py:131-134, the same expressions in the same order.  An integer
+// below 2^32, exact in float64.
+LBDRN_DEV double decoded_term(int img, int msb, float y, float scale, int K)
+{
+    const float rr = __builtin_rintf(y * scale);
+    const int d = img - (int)(uint16_t)((msb << K) + (int)rr);
+    return (double)d * (double)d;
+}
+
 // Sine(w0=30): ref LBDRNmodel.py:13 -- the product 30*z is rounded to float32 first
 LBDRN_DEV float siren_act(float z) { return canon_sin(30.0f * z); }
 

@@ -279,7 +279,66 @@ def build_parser():
     p.add_argument("--nodata-fit", dest="nodata_fit", choices=("all", "valid"), default=argparse.SUPPRESS,
                    help="with --nodata: `valid` trains and ranks the epochs on the valid pixels only (a pixel is void where all its "
                         "bands equal V); `all` (default) fits every pixel.  The .bin format is the same either way")
+    # (absent from the namespace without their flags, like `window`: the records of a run without them stay what they were)
+    goal = p.add_mutually_exclusive_group()
+    goal.add_argument("--target-psnr", dest="target_psnr", type=float, default=argparse.SUPPRESS, metavar="P",
+                      help="fit the K of --target-k side by side and write the smallest file whose closed-loop PSNR is at least P dB")
+    goal.add_argument("--target-bpsp", dest="target_bpsp", type=float, default=argparse.SUPPRESS, metavar="R",
+                      help="likewise, the file of least closed-loop distortion among those of at most R bits per sample")
+    p.add_argument("--target-k", dest="target_k", type=int, nargs=2, default=argparse.SUPPRESS, metavar=("LO", "HI"),
+                   help="with a target: the candidates K = LO..HI (default 1 8; within 1..11)")
+    p.add_argument("--target-peak", dest="target_peak", type=float, default=argparse.SUPPRESS, metavar="P",
+                   help="the peak of the closed-loop PSNR (default 10000, decode.py's `PSNR:` record)")
+    p.add_argument("--report-distortion", dest="report_distortion", action="store_true", default=argparse.SUPPRESS,
+                   help="log the exact closed-loop distortion of the file being written (one `Closed-loop:` record)")
     return p
+
+
+TARGET_ARGS = ("target_psnr", "target_bpsp", "target_k", "target_peak")
+
+
+def target_request(parser, args, sharded=False):
+    """--target-psnr / --target-bpsp and what goes with them, checked before anything is read, fitted or written ->
+    None, or (psnr or None, bpsp or None, [candidate K], peak).  Out of scope, a parser error each: a target or
+    --report-distortion beside --max-error (a different quality contract) or --nodata (the mask step moves samples that
+    decode to V, which the evaluation pass does not see), and a target under a tile-sharded launch."""
+    psnr, bpsp = getattr(args, "target_psnr", None), getattr(args, "target_bpsp", None)
+    wanted = psnr is not None or bpsp is not None
+    report = getattr(args, "report_distortion", False)
+    if hasattr(args, "target_k") and not wanted:
+        parser.error("--target-k names the candidates of --target-psnr / --target-bpsp: it goes with one of them")
+    if hasattr(args, "target_peak") and not (wanted or report):
+        parser.error("--target-peak goes with --target-psnr, --target-bpsp or --report-distortion")
+    lo, hi = getattr(args, "target_k", (1, 8))
+    if not 1 <= lo <= hi <= 11:
+        parser.error(f"--target-k {lo} {hi}: LO <= HI, both within 1..11")
+    peak = getattr(args, "target_peak", 10000.0)
+    if not peak > 0:
+        parser.error(f"--target-peak {peak}: a positive sample value")
+    for flag, on in (("a target", wanted), ("--report-distortion", report)):
+        if on and args.max_error is not None:
+            parser.error(f"{flag} does not go with --max-error: the residual layer is a quality contract of its own")
+        if on and getattr(args, "nodata", None) is not None:
+            parser.error(f"{flag} does not go with --nodata: the mask step moves samples the closed-loop sum does not see")
+    if wanted and sharded:
+        parser.error("a target does not go with a tile-sharded launch: its candidates are fitted side by side on one device")
+    return (psnr, bpsp, list(range(lo, hi + 1)), peak) if wanted else None
+
+
+def tile_distortion(args, res, tile, nn_payload):
+    """the exact closed-loop SSE of one fitted tile (lbdrn_hip.codec.closed_loop_sse): an int"""
+    return codec.closed_loop_sse(res, tile, nn_payload, args.K, args.D, args.base_channel, args.num_layers,
+                                 cfg=FeatCfg.from_constants(), device=DEVICE)
+
+
+def distortion_record(cand, peak):
+    """--report-distortion's record for a whole file (cand: lbdrn_hip.target.Candidate)"""
+    return f"Closed-loop: sse={cand.sse} mse={cand.mse!r} psnr={cand.psnr(peak)!r}"
+
+
+def candidate_record(cand, peak):
+    return (f"Candidate K={cand.K}: bytes={cand.nbytes} bpsp={cand.bpsp!r} sse={cand.sse} mse={cand.mse!r} "
+            f"psnr={cand.psnr(peak)!r}")
 
 
 def scene_tags(args, path, window):
@@ -355,13 +414,17 @@ def main(argv=None, shard_tiles=None):
         container.check_base_codec(BASE_CODEC)
     except ValueError as e:
         parser.error(str(e))
+    if shard_tiles is None:
+        shard_tiles = shard.env_world()[1] > 1
+    target = target_request(parser, args, sharded=shard_tiles)
     check_scene_window(parser, args)
     window = getattr(args, "window", None)
     V = nodata_value(parser, args)
     nodata_fit_mode(parser, args)
+    if target is not None:
+        return main_target(args, target)
+    report = getattr(args, "report_distortion", False)
     rank, world = 0, 1
-    if shard_tiles is None:
-        shard_tiles = shard.env_world()[1] > 1
     if shard_tiles:
         rank, world, local = shard.init_host_group()
         DEVICE = shard.bind_device(local)
@@ -425,6 +488,7 @@ def main(argv=None, shard_tiles=None):
         ahead = BasePayloadsAhead([tile for _, tile in jobs], args.K)
     results = train_tiles(args, jobs, [draws[t] for t in mine]) if jobs else []
     fitted = []   # (tile index, nn payload, MSB payload, captured log records or None, residual body or None[, mask entry])
+    sse = 0       # --report-distortion: the closed-loop sum of this rank's tiles
     for k, (t, (path, tile), res) in enumerate(zip(mine, jobs, results)):
         args.path = path
         take = (lambda k=k: ahead.take(k)) if ahead is not None else None
@@ -444,6 +508,10 @@ def main(argv=None, shard_tiles=None):
             layer = (nodata_layer(args, res, tile, nn, mask) if V is not None else
                      residual_layer(args, res, tile, nn) if args.max_error is not None else None)
         fitted.append((t, nn, base, lines, layer) + ((mask,) if V is not None else ()))      # the mask travels beside the layer
+        if report:
+            sse += tile_distortion(args, res, tile, nn)
+    if report and world > 1:      # (exact integers: the order of the ranks' sums does not matter)
+        sse = sum(shard.all_to_all_objects(sse))
     gathered = shard.gather_to_root(fitted) if world > 1 else [fitted]
     if rank == 0:
         tiles = sorted((rec for part in gathered for rec in part), key=lambda rec: rec[0])
@@ -469,6 +537,10 @@ def main(argv=None, shard_tiles=None):
             logger.log.info(nodata_record)
         if geo_record is not None:
             logger.log.info(geo_record)
+        if report:
+            from lbdrn_hip.target import Candidate
+            logger.log.info(distortion_record(Candidate(args.K, os.path.getsize(bitstream_path), sse, C * height * width),
+                                              getattr(args, "target_peak", 10000.0)))
         logger.log.info(f"Time elapsed: {time.time() - start_time}")
     if world > 1:
         shard.finish()
@@ -481,6 +553,102 @@ def output_folder(args):
     return "{}/{}_r{}_K{}_bc{}_nl{}_D{}_prec{}_lr{}_bs{}_e{}".format(
         args.output_dir, filename, args.split_ratio, args.K, args.base_channel, args.num_layers,
         args.D, args.precision, args.lr, args.batch_size, args.epochs)
+
+
+def main_target(base, target):
+    """main() with --target-psnr P or --target-bpsp R: the candidates K of --target-k are fitted side by side as
+    main_k_points fits them (the raster read and tiled once, one draw per tile, all (tile, K) fits through one
+    codec.fit_many), every candidate's payloads are packed and its two figures taken for the whole scene -- the size of its
+    file and its exact closed-loop SSE (tile_distortion), both sums over the tiles --, lbdrn_hip.target.choose picks one, and
+    ONLY that point is written: into the folder main() with -K k names, the .bin byte for byte that run's, encode.txt that
+    run's records (their times apart) plus one `Candidate` record per K and the `Target:` record.  Unchosen candidates leave
+    nothing on disk.  Where no candidate meets the target the table and a `Target not met` record go to stdout, nothing is
+    written, and the status is 3.  base: the parsed arguments (their -K is ignored); target: target_request's answer."""
+    from lbdrn_hip.target import Candidate, TargetNotMet, choose, describe
+    psnr, bpsp, Ks, peak = target
+    plain = argparse.Namespace(**{k: v for k, v in vars(base).items() if k not in TARGET_ARGS})   # what `-K k` alone parses to
+    window = getattr(base, "window", None)
+    if not base.randomness:
+        torch.manual_seed(base.seed)
+        np.random.seed(base.seed)
+        random.seed(base.seed)
+    org_path = base.path
+    filename = scene_name(base)
+    start_time = time.time()
+    geo_chunk, geo_record = scene_tags(base, org_path, window)
+    tile_reads = tile_reads_wanted() and base.split_ratio > 1
+    if tile_reads:
+        img = None
+        C, height, width = scene_geometry(org_path, window)
+    else:
+        img = raster_io.read_raster(org_path) if window is None else raster_io.read_raster(org_path, window=window)
+        img = img.reshape((-1,) + img.shape[-2:])
+        C, height, width = img.shape
+    windows = list(tile_windows(width, height, base.split_ratio)) if base.split_ratio > 1 else [None]
+    n_feature = FeatCfg.from_constants().feature_dim(C, base.D)
+    draws = [codec.draw_fit(n_feature, base.base_channel, C, base.num_layers, base.epochs, base.val_duration)
+             for _ in windows]      # one draw per tile, in tile order, serves every K
+    tiles = []
+    ahead_tiles = tiles_ahead(org_path, window, windows) if tile_reads else None
+    for win in windows:
+        tile = img
+        if win is not None:
+            i, j, x0, y0, w, h = win
+            tile = next(ahead_tiles) if tile_reads else np.ascontiguousarray(img[:, y0:y0 + h, x0:x0 + w])
+        tiles.append(tile)
+    ahead = {}
+    if BASE_CODEC.lower() in ("jp2", "jpeg2000", "jp2openjpeg") and os.environ.get("LBDRN_JP2_AHEAD", "1") != "0":
+        ahead = {K: BasePayloadsAhead(tiles, K) for K in Ks}
+    entries = [(t, K) for t in range(len(tiles)) for K in Ks]      # tile-major: the K points of a tile are neighbours
+    results = dict(zip(entries, train_tiles_at(base, [tiles[t] for t, _ in entries], [K for _, K in entries],
+                                               [draws[t] for t, _ in entries])))
+    # every candidate reported and packed as main() does it, its records kept aside until one of them is chosen
+    logger.create_logger("", "")      # (stdout; no folder exists yet)
+    table, packed = [], {}
+    for K in Ks:
+        a = argparse.Namespace(**vars(plain))
+        a.K = K
+        a.output_dir = output_folder(a)
+        for t in range(len(tiles)):
+            if isinstance(results[(t, K)], Exception):
+                raise results[(t, K)]
+        tiles_out, sse = [], 0
+        with logger.capture() as lines:
+            for t, (win, tile) in enumerate(zip(windows, tiles)):
+                a.path = org_path if win is None else f"{a.output_dir}/tile_{win[0]}_{win[1]}.tif"
+                take = (lambda t=t, K=K: ahead[K].take(t)) if K in ahead else None
+                logger.log.info(a)
+                nn, base_payload = report_and_pack(a, results[(t, K)], take)
+                sse += tile_distortion(a, results[(t, K)], tile, nn)
+                tiles_out.append((nn, base_payload))
+        header = container.pack_header(a.split_ratio, width, height, K, a.base_channel, a.num_layers, a.D,
+                                       [len(nn) for nn, _ in tiles_out], [len(b) for _, b in tiles_out],
+                                       activation=FeatCfg.from_constants().activation)
+        body = b"".join([header] + [part for rec in tiles_out for part in rec] + [geo_chunk])
+        table.append(Candidate(K, len(body), sse, C * height * width))
+        packed[K] = (a, lines, body)
+    try:
+        won = choose(table, psnr=psnr, bpsp=bpsp, peak=peak)
+    except TargetNotMet:
+        for cand in table:
+            logger.log.info(candidate_record(cand, peak))
+        logger.log.info(f"Target not met: {describe(psnr, bpsp)}")
+        return 3
+    a, lines, body = packed[won.K]
+    os.makedirs(a.output_dir, exist_ok=True)
+    logger.create_logger(a.output_dir, "encode.txt")
+    logger.replay(lines)
+    for cand in table:
+        logger.log.info(candidate_record(cand, peak))
+    logger.log.info(f"Target: {describe(psnr, bpsp)} -> K={won.K}")
+    with open(f"{a.output_dir}/{filename}.bin", "wb") as f:
+        f.write(body)
+    if geo_record is not None:
+        logger.log.info(geo_record)
+    if getattr(base, "report_distortion", False):
+        logger.log.info(distortion_record(won, peak))
+    logger.log.info(f"Time elapsed: {time.time() - start_time}")
+    return 0
 
 
 def main_k_points(argv, Ks):

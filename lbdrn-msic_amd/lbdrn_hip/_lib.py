@@ -9,7 +9,8 @@ EVAL_BACKGROUND = 0x200   # hint OR'ed into `path` of lbdrn_eval_sse
 EVAL_FAST = 0x400         # the per-epoch ranking pass in the tolerance arithmetic (lbdrn_hip.h)
 EVAL_X16 = 0x1000         # with EVAL_FAST, opt-in: layer 0's colour features on the f16 matrix pipe, operands exact (lbdrn_hip.h)
 EVAL_VALID = 0x4000        # lbdrn_geom.reserved holds a nodata value: samples equal to it add no term to the sum (lbdrn_hip.h)
-APPLY_DECODE = 0x2000    # path word of lbdrn_apply_instance only: the request lbdrn_decode_fused makes (lbdrn_hip.h)
+EVAL_DECODED = 0x8000      # the closed-loop sum: a term is (img - out)^2, out the sample lbdrn_decode_fused writes; exact (lbdrn_hip.h)
+APPLY_DECODE = 0x2000   # path word of lbdrn_apply_instance only: the request lbdrn_decode_fused makes (lbdrn_hip.h)
 TRAIN_ALONE = 0x800      # hint OR'ed into `path` of lbdrn_train_epoch: nothing else in flight on the device (lbdrn_hip.h)
 
 

@@ -860,6 +860,30 @@ def _closed_loop_recon(fit_result, img, nn_payload, K, D, base_channel, num_laye
     return orig_d, ops.decode_fused(geom, net, msb_d, p, path=path).contiguous()
 
 
+def closed_loop_sse(fit_result, img, nn_payload, K, D, base_channel, num_layers, cfg=None, device="cuda:0",
+                    path=ops.PATH_AUTO):
+    """The exact sum over all samples of (img - recon)^2 as a Python int, recon being what every decoder of this package
+    reconstructs from the fit's MSB planes and `nn_payload` (the weights AFTER their payload round trip, as in
+    _closed_loop_recon) -- without reconstructing it: one evaluation pass with LBDRN_EVAL_DECODED (lbdrn_hip.h: the integer
+    is exact below 2^53), no raster allocated, one host read."""
+    from . import container
+    cfg = cfg or FeatCfg.from_constants()
+    dev = torch.device(device)
+    msb_d = fit_result.msb_device
+    C, H, W = msb_d.shape
+    orig_d = ops.to_device_u16(_as_planes(img), dev)
+    if tuple(orig_d.shape) != (C, H, W):
+        raise ValueError(f"the original is {tuple(orig_d.shape)}, the fit's planes are {(C, H, W)}")
+    geom = ops.FeatureGeometry(C, H, W, K, D, fit_result.msb_max, cfg, dev)
+    net = ops.make_net(geom.F, base_channel, C, num_layers, cfg.act)
+    params = container.decode_weights(nn_payload, expected=ops.param_count(net))
+    p = torch.from_numpy(np.ascontiguousarray(params, dtype=np.float32)).to(dev)
+    sse = float(ops.eval_sse(geom, net, orig_d, msb_d, p, path=path, decoded=True).item())
+    if not (sse < 2.0 ** 53 and sse == int(sse)):
+        raise ops._lib.LbdrnError(f"closed-loop SSE {sse!r} is not an exact integer below 2^53")
+    return int(sse)
+
+
 def residual_encode(fit_result, tau, img, nn_payload, K, D, base_channel, num_layers, cfg=None, device="cuda:0",
                     path=ops.PATH_AUTO, nodata=None):
     """The residual layer of one fitted tile -> (LBR1 body, max |orig - recon'| as verified).

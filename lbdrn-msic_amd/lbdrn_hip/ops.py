@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import EVAL_BACKGROUND, EVAL_FAST, EVAL_VALID, EVAL_X16, TRAIN_ALONE, Geom, Net, PATH_AUTO, check, lib
+from ._lib import EVAL_BACKGROUND, EVAL_DECODED, EVAL_FAST, EVAL_VALID, EVAL_X16, TRAIN_ALONE, Geom, Net, PATH_AUTO, check, lib
 
 
 def _call(fn, ref, *args):
@@ -182,8 +182,10 @@ def decode_fused(geom, net, msb, params, want_y=False, path=PATH_AUTO, ws=None):
 
 
 def eval_sse(geom, net, img, msb, params, path=PATH_AUTO, ws=None, out=None, background=False, fast=False, x16=False,
-             nodata=None):
+             nodata=None, decoded=False):
     """Whole-image sum of squared error as a device float64 scalar tensor (no sync).
+    decoded: the closed-loop sum (LBDRN_EVAL_DECODED) -- a term is (img - out)^2 with out the sample decode_fused writes for
+    the same arguments, an exact integer below 2^53; canonical arithmetic only (with fast the library answers E_ARG).
     nodata: a sample value V (0..65535); the sum then runs over the samples with img != V only (LBDRN_EVAL_VALID: the
     value travels in a copy of the geometry's `reserved` field, the caller's struct is left as it is).
     background: launch on half as many workgroups (LBDRN_EVAL_BACKGROUND, lbdrn_hip.h); same sum bit for bit.
@@ -203,7 +205,8 @@ def eval_sse(geom, net, img, msb, params, path=PATH_AUTO, ws=None, out=None, bac
     _call(lib().lbdrn_eval_sse, msb, ctypes.byref(gc), ctypes.byref(net), _ptr(img), _ptr(msb),
                                _ptr(params), _ptr(sse), _ptr(ws.buf), ws.nbytes,
                                path | (EVAL_BACKGROUND if background else 0) | (EVAL_FAST if fast else 0) |
-                               (EVAL_X16 if (fast and x16) else 0) | (EVAL_VALID if nodata is not None else 0))
+                               (EVAL_X16 if (fast and x16) else 0) | (EVAL_VALID if nodata is not None else 0) |
+                               (EVAL_DECODED if decoded else 0))
     return sse
 
 
